@@ -1,8 +1,17 @@
 """Training throughput benchmark (BASELINE.json metric: training images/sec at
 640x192 mono, 1/2/4/8 GPUs; loss delta vs reference).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(metric, value, unit, ms_per_step, ...); --dump-outputs DIR also writes what the last
+timed step returned as DIR/<name>.npy.  Weights and inputs are seeded and the
+convolution kernels are pinned per shape to monodepth2_amd/conv_choices.json
+(--conv-choices; `auto` times them in the run instead), so the same arguments give
+the same inputs and, at the shapes the table lists, the same output bits on every
+run.  Everything under "Extra fields" below
+takes runs of its own and is measured only with --full (null in a plain line).
 
 Workload (configs[1] of BASELINE.json): mono 640x192, ResNet-18 depth encoder +
 DepthDecoder + separate ResNet-18 pose encoder + PoseDecoder, frame_ids [0,-1,1],
@@ -13,7 +22,7 @@ init weights (no network for ImageNet weights).  Data parallel: one process per
 GPU, each with its own 12-image shard (weak scaling), DDP gradient all-reduce over
 RCCL.  Rank 0 prints ONE JSON line.
 
-Extra fields:
+Extra fields (--full):
   roofline      — the fused hot path (md2_photometric_fwd + md2_photometric_bwd: every
                   kernel of it), HIP-event timed on its launch stream during the timed
                   steps (first kernel's start to last kernel's end of each call).
@@ -35,10 +44,13 @@ Extra fields:
                   (generate_images_pred + compute_losses, trainer.py:341-496) as eager
                   ATen ops on the same GPU, fwd+bwd on the step's own outputs; the
                   ratio to the HIP hot path is context, never the target.
+  host_enqueue_ms_per_step — the CPU time to issue a step (3 extra steps before the
+                  timed ones); conv_roofline — the split-bf16 convolution alone.
 """
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -51,6 +63,30 @@ sys.path.insert(0, REPO)
 # immediate-mode heuristic, never an exhaustive search (see monodepth2_amd/__init__.py)
 if "--miopen-find" in sys.argv:
     os.environ["MIOPEN_FIND_MODE"] = sys.argv[sys.argv.index("--miopen-find") + 1].upper()
+
+
+def _scratch_miopen_db():
+    """MIOpen opens its user find-db and kernel cache (SQLite) for writing, and appends
+    what it compiles: in a checkout this user cannot write, the first convolution fails
+    with miopenStatusInternalError ("attempt to write a readonly database").  So the run
+    works on a scratch copy of the shipped monodepth2_amd/miopen_db, same contents, removed
+    at exit; the committed files are only read.  A caller's own MIOPEN_USER_DB_PATH /
+    MIOPEN_CUSTOM_CACHE_DIR stays (the PMC child runs inherit this run's copy that way)."""
+    names = ("MIOPEN_USER_DB_PATH", "MIOPEN_CUSTOM_CACHE_DIR")
+    if any(n in os.environ for n in names):
+        return
+    import atexit
+    import shutil
+    import tempfile
+    d = tempfile.mkdtemp(prefix="md2_miopen_db_")
+    for f in os.listdir(os.path.join(REPO, "monodepth2_amd", "miopen_db")):
+        shutil.copyfile(os.path.join(REPO, "monodepth2_amd", "miopen_db", f), os.path.join(d, f))
+    atexit.register(shutil.rmtree, d, ignore_errors=True)
+    for n in names:
+        os.environ[n] = d
+
+
+_scratch_miopen_db()
 import monodepth2_amd  # noqa: E402,F401  (sets the MIOpen environment before torch loads MIOpen)
 
 import torch  # noqa: E402
@@ -62,6 +98,8 @@ F32_MFMA_PEAK_TFLOPS = 157.3   # MI355X_MICROARCH.md, dense f32 matrix (= f32 ve
 F32_VALU_PEAK_TFLOPS = 157.3   # MI355X_MICROARCH.md, "Peak FP32 (vector)"
 BF16_MFMA_PEAK_TFLOPS = 2500.0 # dense bf16; the split-bf16 convs issue 6 bf16 products per f32 product
 ROUND = "r03"
+# the committed table of the bench shapes (fp32, batch 12, 640x192 ResNet-18)
+CONV_CHOICES = os.path.join(REPO, "monodepth2_amd", "conv_choices.json")
 
 
 HOT_KERNELS = "pack_src8|photo_|smooth_fwd|finalize_fwd|disp_grad|grad_T_kernel"
@@ -71,8 +109,8 @@ def pmc_traffic(args, S, timeout=150):
     """HBM bytes per hot-path step (forward + backward), measured now: two rocprofv3
     --pmc passes (FETCH_SIZE, WRITE_SIZE: one pass cannot hold both) over a short run
     of this same training step (bench.py --steps 3 at the same shape, so the caches
-    hold what they hold in the timed steps), averaged per dispatch per kernel and
-    summed over the hot path's kernels.  FETCH_SIZE x2 (gfx950 under-reports wide
+    hold what they hold in the timed steps; a plain run: nothing but the steps),
+    averaged per dispatch per kernel and summed over the hot path's kernels.  FETCH_SIZE x2 (gfx950 under-reports wide
     reads by half, MI355X_MICROARCH.md §HBM), KB -> bytes.  Runs in child processes
     while this one waits (no GPU work of its own in flight)."""
     import csv
@@ -92,11 +130,12 @@ def pmc_traffic(args, S, timeout=150):
                "--output-format", "csv", "--", sys.executable, os.path.join(REPO, "bench.py"),
                "--batch", str(args.batch), "--height", str(args.height), "--width", str(args.width),
                "--num_layers", str(args.num_layers), "--amp", args.amp, "--steps", "3", "--warmup", "2",
-               "--no-cpu-baseline", "--no-parity", "--pmc", "0", "--no-conv-roofline", "--no-eager-aten", "--graph", "0",
-               "--src8", "0"] + \
+               "--graph", "0", "--src8", "0", "--conv-choices", args.conv_choices] + \
               (["--stereo"] if args.stereo else [])
         env = dict(os.environ, TMPDIR="/tmp")
-        p = subprocess.Popen(cmd, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, env=env, start_new_session=True)
+        # cwd: rocprofv3 leaves a .rocprofv3/ scratch directory where it runs
+        p = subprocess.Popen(cmd, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, env=env, cwd=d,
+                             start_new_session=True)
         try:
             _, err = p.communicate(timeout=timeout)
         except subprocess.TimeoutExpired:
@@ -148,6 +187,16 @@ def parse():
     ap.add_argument("--frame-ids", type=str, default="0,-1,1",
                     help="comma list (trainer --frame_ids): e.g. '0' with --stereo is the stereo-only step "
                          "(no pose network; an experiment, not the headline)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: loss delta vs the oracle, host enqueue "
+                         "time, hot-path roofline + PMC traffic, eager ATen hot path, conv roofline, CPU baseline "
+                         "(each with its own --no-... / --pmc 0 switch); off: the timed steps only")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write what the last timed step returned (its losses and outputs) as DIR/<name>.npy")
+    ap.add_argument("--conv-choices", type=str, default=CONV_CHOICES, metavar="TABLE|auto",
+                    help="per-shape convolution kernel table (tools/conv_choices.py output) the step is pinned to, "
+                         "so that every run computes the same bits; shapes it lacks are timed at the first step.  "
+                         "auto: every shape timed in this run (the kernels, and the rounding, vary run to run)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the CPU baseline sample")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
@@ -176,7 +225,13 @@ def parse():
     ap.add_argument("--gpu-augment", type=int, default=0,
                     help="1: every step also runs the input pipeline (flip + LANCZOS pyramid + jitter, "
                          "md2_aug_run) from resident 375x1242 uint8 frames")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.conv_choices != "auto":
+        args.conv_choices = os.path.abspath(args.conv_choices)
+    if not args.full:
+        args.no_cpu_baseline = args.no_parity = args.no_conv_roofline = args.no_eager_aten = True
+        args.pmc = 0
+    return args
 
 
 def make_trainer(args, device, rank, world):
@@ -402,6 +457,38 @@ def make_augmenting_source(args, frame_ids, device, rank):
     return lambda: aug(frames, [draw_item(rng) for _ in range(args.batch)])
 
 
+DUMP_LIMIT = 64 * 10 ** 6   # bytes a --dump-outputs directory may hold in all
+
+
+def dump_outputs(dirname, outputs, losses):
+    """What a caller of Trainer.train_step received from the last timed step, as
+    <dirname>/<name>.npy: every loss ("loss", "loss_<scale>") and every tensor of the
+    outputs dict (("disp", 0) -> disp_0.npy, ("cam_T_cam", 0, -1) -> cam_T_cam_0_-1.npy,
+    "identity_selection/0" -> identity_selection_0.npy), float32 (float64 kept).  If all
+    of them exceed DUMP_LIMIT, every array above 64 KiB is cut to a fixed, seeded sample
+    of its flattened elements (the same indices on every run, in index order)."""
+    import numpy as np
+    arrays = {}
+    for k, v in list(losses.items()) + list(outputs.items()):
+        if not torch.is_tensor(v):
+            continue
+        name = "_".join(str(p) for p in k) if isinstance(k, tuple) else str(k)
+        name = name.replace("/", "_")
+        assert name not in arrays, name
+        v = v.detach()
+        arrays[name] = v.to(torch.float64 if v.dtype == torch.float64 else torch.float32).cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    frac = 0.9 * DUMP_LIMIT / max(total, 1)
+    rng = np.random.default_rng(0)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in sorted(arrays.items()):
+        if total > DUMP_LIMIT and a.nbytes > 65536:
+            idx = np.sort(rng.choice(a.size, max(65536 // a.itemsize, int(a.size * frac)), replace=False))
+            a = a.ravel()[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    log(f"outputs of the last timed step: {len(arrays)} arrays in {dirname}")
+
+
 def main():
     args = parse()
     from monodepth2_amd.distributed import init_process_group
@@ -419,6 +506,12 @@ def main():
 
     if args.graph < 0:
         args.graph = 1 if world == 1 else 0
+    torch.manual_seed(0)   # the random-init weights: the same on every run (and every rank)
+    if args.conv_choices != "auto" and not os.environ.get("MD2_CONV_CHOICES"):
+        # the same kernel per convolution shape in every run: with timed choices two runs
+        # round differently, and 25 training steps amplify that to 1e-1 in single disparities
+        from monodepth2_amd import conv_ops
+        log(f"convolution choices pinned: {conv_ops.load_choices(args.conv_choices)} shapes of {args.conv_choices}")
     try:
         trainer = make_trainer(args, device, rank, world)
     except ValueError as e:   # e.g. --graph 1 at N > 1 on a non-RCCL backend (Trainer refuses it)
@@ -462,21 +555,23 @@ def main():
             next_batch = lambda: static   # noqa: E731
     stop_hb.set()
     torch.cuda.synchronize()
-    # host enqueue rate: how long the CPU takes to issue 3 steps right after a sync
-    # (<< 3 x ms_per_step means the GPU, not the launch path, bounds the step)
-    t = time.perf_counter()
-    for _ in range(3):
-        trainer.train_step(next_batch())
-    host_ms = 1e3 * (time.perf_counter() - t) / 3
-    torch.cuda.synchronize()
-    log(f"host enqueue time: {host_ms:.2f} ms/step")
+    host_ms = None
+    if args.full:
+        # host enqueue rate: how long the CPU takes to issue 3 steps right after a sync
+        # (<< 3 x ms_per_step means the GPU, not the launch path, bounds the step)
+        t = time.perf_counter()
+        for _ in range(3):
+            trainer.train_step(next_batch())
+        host_ms = 1e3 * (time.perf_counter() - t) / 3
+        torch.cuda.synchronize()
+        log(f"host enqueue time: {host_ms:.2f} ms/step")
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    with _lib.KernelTimer(max_launches=8 * args.steps + 16) as kt:
+    with (_lib.KernelTimer(max_launches=8 * args.steps + 16) if args.full else contextlib.nullcontext()) as kt:
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            _, losses = trainer.train_step(next_batch())
+            outputs, losses = trainer.train_step(next_batch())
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -487,87 +582,92 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t)
     final_loss = float(losses["loss"])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs, losses)
 
     timed_standalone = False
-    if rank == 0 and kt.n_bwd == 0:
+    if rank == 0 and args.full and kt.n_bwd == 0:
         kt = time_hot_kernels(trainer, batch)
         timed_standalone = True
         log("hot-path kernels timed stand-alone (graph mode)")
     if rank == 0:
         S = len(frame_ids) - 1
         B, H, W = args.batch, args.height, args.width
-        bwd_ms = kt.bwd_ms / max(kt.n_bwd, 1)
-        fwd_ms = kt.fwd_ms / max(kt.n_fwd, 1)
-        fcall = kt.fwd_call_ms / max(kt.n_fwd_call, 1)
-        bcall = kt.bwd_call_ms / max(kt.n_bwd_call, 1)
-        hot_ms = fcall + bcall
-        from monodepth2_amd.roofline import hot_path_census
-        cen = hot_path_census(H, W, S)
-        step_bytes, step_flops = B * cen.bytes, B * cen.flops
-        gbs = step_bytes / (hot_ms * 1e-3) / 1e9
-        tfs = step_flops / (hot_ms * 1e-3) / 1e12
-        hbm_frac, valu_frac = gbs / HBM_PEAK_GBS, tfs / F32_VALU_PEAK_TFLOPS
-        traffic, pmc_note, pmc_kernels, pack_traffic = None, "skipped (--pmc 0 or N>1)", None, None
-        if args.pmc and world == 1:
-            pmc_kernels, err = pmc_traffic(args, S)
-            if pmc_kernels is not None:
-                # the PMC child runs without the loader's 8-bit copies (--src8 0), so its
-                # forward packs them (pack_src8_kernel); the other kernels read the same
-                # RGBx dwords either way
-                pack_traffic = sum(v["corrected"] for k, v in pmc_kernels.items() if k.startswith("pack_src8"))
-                traffic = sum(v["corrected"] for k, v in pmc_kernels.items() if not k.startswith("pack_src8"))
-                pmc_note = ("rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes in this run over a 3-step run of this "
-                            "training step (bench.py --steps 3); per dispatch, summed over the hot path's kernels: "
-                            "2*FETCH+WRITE (KB->B), the x2 calibrated for the 4/8/16-B-per-lane reads these kernels "
-                            "issue (tools/fetch_calib.py, profiles/r04/fetch_calib.json); raw = FETCH+WRITE per "
-                            "kernel beside it")
+        roof, hot_ms = None, None
+        if args.full:
+            bwd_ms = kt.bwd_ms / max(kt.n_bwd, 1)
+            fwd_ms = kt.fwd_ms / max(kt.n_fwd, 1)
+            fcall = kt.fwd_call_ms / max(kt.n_fwd_call, 1)
+            bcall = kt.bwd_call_ms / max(kt.n_bwd_call, 1)
+            hot_ms = fcall + bcall
+            from monodepth2_amd.roofline import hot_path_census
+            cen = hot_path_census(H, W, S)
+            step_bytes, step_flops = B * cen.bytes, B * cen.flops
+            gbs = step_bytes / (hot_ms * 1e-3) / 1e9
+            tfs = step_flops / (hot_ms * 1e-3) / 1e12
+            hbm_frac, valu_frac = gbs / HBM_PEAK_GBS, tfs / F32_VALU_PEAK_TFLOPS
+            traffic, pmc_note, pmc_kernels, pack_traffic = None, "skipped (--pmc 0 or N>1)", None, None
+            if args.pmc and world == 1:
+                pmc_kernels, err = pmc_traffic(args, S)
+                if pmc_kernels is not None:
+                    # the PMC child runs without the loader's 8-bit copies (--src8 0), so its
+                    # forward packs them (pack_src8_kernel); the other kernels read the same
+                    # RGBx dwords either way
+                    pack_traffic = sum(v["corrected"] for k, v in pmc_kernels.items() if k.startswith("pack_src8"))
+                    traffic = sum(v["corrected"] for k, v in pmc_kernels.items() if not k.startswith("pack_src8"))
+                    pmc_note = ("rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes in this run over a 3-step run of this "
+                                "training step (bench.py --steps 3); per dispatch, summed over the hot path's kernels: "
+                                "2*FETCH+WRITE (KB->B), the x2 calibrated for the 4/8/16-B-per-lane reads these kernels "
+                                "issue (tools/fetch_calib.py, profiles/r04/fetch_calib.json); raw = FETCH+WRITE per "
+                                "kernel beside it")
+                else:
+                    pmc_note = err
+                log(f"pmc traffic: {traffic} B/step ({pmc_note[:80]})")
+            # the sources' RGBx copies: handed in with the batch (md2_aug_run2 writes them as it
+            # decodes; data.pack_rgbx for the resident bench batch), or packed by the forward
+            # from the reference's fp32 colours (mono_dataset.py:199-200's to_tensor output):
+            # that conversion timed beside the headline
+            pack = None
+            if "color_src8" in batch:
+                k0, k1 = time_hot_kernels(trainer, batch, src8=False), time_hot_kernels(trainer, batch)
+                pack_ms = max(k0.fwd_call_ms / max(k0.n_fwd_call, 1) - k1.fwd_call_ms / max(k1.n_fwd_call, 1), 0.0)
+                hot_pack = hot_ms + pack_ms
+                pack = {"src8": "loader", "pack_ms": round(pack_ms, 5),
+                        "pack_timing": "fwd call without the loader's copies (pack_src8_kernel + the walk) minus "
+                                       "the fwd call with them, stand-alone, same tensors",
+                        "pack_traffic": pack_traffic,
+                        "hot_path_ms_with_pack": round(hot_pack, 5),
+                        "valu_frac_with_pack": round(step_flops / (hot_pack * 1e-3) / 1e12 / F32_VALU_PEAK_TFLOPS, 5),
+                        "traffic_with_pack": (traffic + pack_traffic) if (traffic is not None and pack_traffic)
+                        else None}
+                log(f"src8 pack: {pack_ms:.4f} ms, {pack_traffic} B")
+            head = ("valu", tfs, F32_VALU_PEAK_TFLOPS, "TFLOP/s", valu_frac) if valu_frac >= hbm_frac else \
+                ("hbm", gbs, HBM_PEAK_GBS, "GB/s", hbm_frac)
+            roof = {"bound": head[0], "kernel": "hot path: md2_photometric_fwd + md2_photometric_bwd (all their kernels)",
+                    "achieved": round(head[1], 3), "peak": head[2], "unit": head[3], "frac": round(head[4], 5),
+                    "traffic": traffic,
+                    "algorithmic_bytes_per_step": int(step_bytes), "algorithmic_flops_per_step": int(step_flops),
+                    "census": {"bytes_per_px": cen.bytes / (H * W), "fwd_flops_per_px": cen.fwd_flops / (H * W),
+                               "bwd_flops_per_px": cen.bwd_flops / (H * W), "source": "monodepth2_amd/roofline.py"},
+                    "hbm": {"achieved_gbs": round(gbs, 2), "peak": HBM_PEAK_GBS, "frac": round(hbm_frac, 5)},
+                    "valu": {"achieved_tflops": round(tfs, 3), "peak": F32_VALU_PEAK_TFLOPS, "frac": round(valu_frac, 5)},
+                    "avg_ms_per_step": round(hot_ms, 5), "fwd_call_ms": round(fcall, 5), "bwd_call_ms": round(bcall, 5),
+                    "timing": ("stand-alone: HIP events on the step's own tensors right after the timed replays "
+                               "(a captured step's kernels are not individually instrumented)" if timed_standalone
+                               else "in the timed steps: HIP events the library stamps on each call's first and last "
+                                    "kernel, on the launch stream"),
+                    "calls": kt.n_bwd_call, "traffic_source": pmc_note, "traffic_by_kernel": pmc_kernels,
+                    "photo_bwd": {"avg_launch_ms": round(bwd_ms, 5), "launches": kt.n_bwd,
+                                  "share_of_hot_path": round(bwd_ms / hot_ms, 3) if hot_ms else None},
+                    "photo_fwd_kernels_ms": round(fwd_ms, 5)}
+            if pack is not None:
+                roof.update(pack)
             else:
-                pmc_note = err
-            log(f"pmc traffic: {traffic} B/step ({pmc_note[:80]})")
-        # the sources' RGBx copies: handed in with the batch (md2_aug_run2 writes them as it
-        # decodes; data.pack_rgbx for the resident bench batch), or packed by the forward
-        # from the reference's fp32 colours (mono_dataset.py:199-200's to_tensor output):
-        # that conversion timed beside the headline
-        pack = None
-        if "color_src8" in batch:
-            k0, k1 = time_hot_kernels(trainer, batch, src8=False), time_hot_kernels(trainer, batch)
-            pack_ms = max(k0.fwd_call_ms / max(k0.n_fwd_call, 1) - k1.fwd_call_ms / max(k1.n_fwd_call, 1), 0.0)
-            hot_pack = hot_ms + pack_ms
-            pack = {"src8": "loader", "pack_ms": round(pack_ms, 5),
-                    "pack_timing": "fwd call without the loader's copies (pack_src8_kernel + the walk) minus "
-                                   "the fwd call with them, stand-alone, same tensors",
-                    "pack_traffic": pack_traffic,
-                    "hot_path_ms_with_pack": round(hot_pack, 5),
-                    "valu_frac_with_pack": round(step_flops / (hot_pack * 1e-3) / 1e12 / F32_VALU_PEAK_TFLOPS, 5),
-                    "traffic_with_pack": (traffic + pack_traffic) if (traffic is not None and pack_traffic)
-                    else None}
-            log(f"src8 pack: {pack_ms:.4f} ms, {pack_traffic} B")
-        head = ("valu", tfs, F32_VALU_PEAK_TFLOPS, "TFLOP/s", valu_frac) if valu_frac >= hbm_frac else \
-            ("hbm", gbs, HBM_PEAK_GBS, "GB/s", hbm_frac)
-        roof = {"bound": head[0], "kernel": "hot path: md2_photometric_fwd + md2_photometric_bwd (all their kernels)",
-                "achieved": round(head[1], 3), "peak": head[2], "unit": head[3], "frac": round(head[4], 5),
-                "traffic": traffic,
-                "algorithmic_bytes_per_step": int(step_bytes), "algorithmic_flops_per_step": int(step_flops),
-                "census": {"bytes_per_px": cen.bytes / (H * W), "fwd_flops_per_px": cen.fwd_flops / (H * W),
-                           "bwd_flops_per_px": cen.bwd_flops / (H * W), "source": "monodepth2_amd/roofline.py"},
-                "hbm": {"achieved_gbs": round(gbs, 2), "peak": HBM_PEAK_GBS, "frac": round(hbm_frac, 5)},
-                "valu": {"achieved_tflops": round(tfs, 3), "peak": F32_VALU_PEAK_TFLOPS, "frac": round(valu_frac, 5)},
-                "avg_ms_per_step": round(hot_ms, 5), "fwd_call_ms": round(fcall, 5), "bwd_call_ms": round(bcall, 5),
-                "timing": ("stand-alone: HIP events on the step's own tensors right after the timed replays "
-                           "(a captured step's kernels are not individually instrumented)" if timed_standalone
-                           else "in the timed steps: HIP events the library stamps on each call's first and last "
-                                "kernel, on the launch stream"),
-                "calls": kt.n_bwd_call, "traffic_source": pmc_note, "traffic_by_kernel": pmc_kernels,
-                "photo_bwd": {"avg_launch_ms": round(bwd_ms, 5), "launches": kt.n_bwd,
-                              "share_of_hot_path": round(bwd_ms / hot_ms, 3) if hot_ms else None},
-                "photo_fwd_kernels_ms": round(fwd_ms, 5)}
-        if pack is not None:
-            roof.update(pack)
-        else:
-            roof["src8"] = "packed in the forward (counted in the headline)"
-        log(f"timed: {1e3 * dt / args.steps:.2f} ms/step, hot path {hot_ms:.3f} ms (fwd {fcall:.3f}, bwd {bcall:.3f};"
-            f" photo_bwd {bwd_ms:.3f}), {tfs:.2f} TF = {valu_frac:.3f} of VALU peak, {gbs:.0f} GB/s, "
-            f"adam table uploads {getattr(trainer.model_optimizer, 'rebuilds', '-')}")
+                roof["src8"] = "packed in the forward (counted in the headline)"
+        log(f"timed: {1e3 * dt / args.steps:.2f} ms/step, "
+            + (f"hot path {hot_ms:.3f} ms (fwd {fcall:.3f}, bwd {bcall:.3f}; photo_bwd {bwd_ms:.3f}), "
+               f"{tfs:.2f} TF = {valu_frac:.3f} of VALU peak, {gbs:.0f} GB/s, " if args.full else "")
+            + f"adam table uploads {getattr(trainer.model_optimizer, 'rebuilds', '-')}")
         eager_ms = None
         if not args.no_eager_aten:
             eager_ms = eager_aten_hot_path(trainer, batch)
@@ -606,7 +706,7 @@ def main():
                             "hot path (roofline.avg_ms_per_step), same GPU, same run, same B=%d inputs, the "
                             "step's own disparities and transforms" % B} if eager_ms is not None else None),
                 "loss_delta_vs_oracle": delta, "final_loss": round(final_loss, 6),
-                "host_enqueue_ms_per_step": round(host_ms, 3)}
+                "host_enqueue_ms_per_step": round(host_ms, 3) if host_ms is not None else None}
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()
