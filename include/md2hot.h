@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define MD2_ABI_VERSION 23
+#define MD2_ABI_VERSION 24
 #define MD2_MAX_SCALES 4
 #define MD2_MAX_SRC 3
 
@@ -633,6 +633,71 @@ int md2_conv_direct(const md2_conv_desc* desc, const float* x, const float* wk, 
 size_t md2_conv_wgrad_direct_workspace_bytes(const md2_conv_desc* desc);
 int md2_conv_wgrad_direct(const md2_conv_desc* desc, const float* x, const float* grad_y, float* grad_weight,
                           void* workspace, void* stream);
+
+/*
+ * KITTI depth evaluation (ABI 24, csrc/eval.hip): the per-image body of the reference's
+ * evaluate_depth.py:181-214 (resize the disparity to the ground-truth map, mask, median
+ * scaling, clamp, compute_errors 27-45, batch_post_process_disparity 48-56) and of
+ * Trainer.compute_depth_losses (trainer.py:498-526) as one chain of launches on `stream`:
+ * no boolean indexing, no host-side median, nothing returns to the host.
+ *
+ * disp (B,1,height,width): the network's sigmoid output (disp_to_depth's scaling with
+ * min_depth / max_depth, layers.py:16-25, happens here); disp_flipped: the same for the
+ * horizontally flipped images (MD2_EVAL_POST_PROCESS; else may be NULL); gt
+ * (B,gt_height,gt_width), 0 = no measurement.  Per ground-truth pixel:
+ *   default              pred = scale_factor / bilinear(scaled disparity)   (evaluate_depth.py)
+ *   MD2_EVAL_RESIZE_DEPTH pred = scale_factor * clamp(bilinear(1 / scaled disparity),
+ *                                eval_min, eval_max)                (compute_depth_losses)
+ * bilinear = half-pixel centres, src = (dst + 0.5) * in / out - 0.5, negative coordinates
+ * clamped to 0, the upper neighbour clamped to the edge (F.interpolate, align_corners=
+ * False).  A pixel is valid when gt > 0 (MD2_EVAL_GT_RANGE: eval_min < gt < eval_max) and
+ * it lies in the crop rectangle [crop_y0, crop_y1) x [crop_x0, crop_x1).  A population is
+ * the valid pixels of one image, or of the whole batch with MD2_EVAL_POOL_BATCH.  With
+ * MD2_EVAL_MEDIAN_SCALE pred *= median(gt) / median(pred) over the population, the
+ * medians being exact order statistics of the fp32 values (four 8-bit radix passes over
+ * their bit patterns): the element at (n-1)/2 with MD2_EVAL_MEDIAN_LOWER (torch.median),
+ * else the mean of the elements at (n-1)/2 and n/2 (np.median).  Then pred is clamped to
+ * [eval_min, eval_max] and the seven metrics are reduced: fixed per-block trees, the block
+ * partials summed in block order, all in fp64; the threshold counts are integers.
+ * disp_to_depth is torch's fp32 product and sum; the arithmetic between it and the fp32
+ * pred (post-processing, resize, inversion) is fp64, rounded once.  min_depth 1 with
+ * max_depth INFINITY makes that scaling the identity (disp already scaled).
+ *
+ * out: P x 10 floats, P = B (or 1 with POOL_BATCH): abs_rel, sq_rel, rmse, rmse_log, a1,
+ * a2, a3, the median ratio applied (1 without MEDIAN_SCALE), the valid-pixel count, 0
+ * (reserved).  A population without a valid pixel gets count 0 and NaN in the first eight.
+ * workspace: the size the function below returns, no initialisation needed; after the call its
+ * first B * gt_height * gt_width floats hold pred before the median scaling (bit pattern
+ * 0xFFFFFFFF at invalid pixels).  Deterministic, hipGraph-capturable.
+ */
+#define MD2_EVAL_POST_PROCESS (1u << 0)
+#define MD2_EVAL_RESIZE_DEPTH (1u << 1)
+#define MD2_EVAL_GT_RANGE     (1u << 2)
+#define MD2_EVAL_MEDIAN_SCALE (1u << 3)
+#define MD2_EVAL_MEDIAN_LOWER (1u << 4)
+#define MD2_EVAL_POOL_BATCH   (1u << 5)
+#define MD2_EVAL_OUT 10   /* floats per population */
+
+typedef struct md2_eval_desc {
+    int32_t batch;                  /* B */
+    int32_t height, width;          /* of disp (the network's scale-0 map) */
+    int32_t gt_height, gt_width;    /* of gt */
+    int32_t crop_y0, crop_y1, crop_x0, crop_x1; /* within the gt map; the whole map = no crop */
+    uint32_t flags;                 /* MD2_EVAL_* */
+    double min_depth, max_depth;    /* opt.min_depth / opt.max_depth of disp_to_depth, as the
+                                       Python doubles (offset 40): lo = fp32(1 / max_depth) and
+                                       range = fp32(1 / min_depth - 1 / max_depth) are then the
+                                       fp32 scalars torch multiplies and adds for any value */
+    float eval_min, eval_max;       /* MIN_DEPTH / MAX_DEPTH of the evaluation (1e-3, 80) */
+    double scale_factor;            /* opt.pred_depth_scale_factor (5.4 for stereo); a double (at
+                                       offset 56) because it multiplies every prediction: the
+                                       fp32 of 5.4 alone is off by 1.8e-8; offset 64, the struct is 72 bytes */
+} md2_eval_desc;
+
+/* 0 (and md2_last_error) for a desc md2_depth_eval would refuse */
+size_t md2_depth_eval_workspace_bytes(const md2_eval_desc* desc);
+int md2_depth_eval(const md2_eval_desc* desc, const float* disp, const float* disp_flipped, const float* gt,
+                   float* out, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }

@@ -21,7 +21,7 @@ LIB_PATH = os.environ.get("MD2_LIB", _BUILT_LIB)
 
 MAX_SCALES = 4
 MAX_SRC = 3
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 NO_SSIM = 1 << 0
 AVG_REPROJECTION = 1 << 1
@@ -69,7 +69,8 @@ EXPORTS = ["md2_abi_version", "md2_last_error", "md2_workspace_bytes", "md2_sele
            "md2_conv_dgrad", "md2_conv_wgrad", "md2_conv_direct", "md2_conv_wgrad_direct",
            "md2_conv_wgrad_direct_workspace_bytes", "md2_conv_split_weights_multi", "md2_bn_fwd_mask",
            "md2_bn_bwd_mask", "md2_build_id", "md2_maxpool3s2_bwd_multi", "md2_decoder_pad_bwd2", "md2_aug_run2",
-           "md2_conv_bf16_weights", "md2_conv_bf16_weights_multi"]
+           "md2_conv_bf16_weights", "md2_conv_bf16_weights_multi",
+           "md2_depth_eval", "md2_depth_eval_workspace_bytes"]
 
 DTYPE_F32 = 0    # md2_desc.disp_dtype
 DTYPE_BF16 = 1
@@ -166,7 +167,31 @@ class BiasActDesc(ctypes.Structure):
     _fields_ = [("pixels", ctypes.c_int64), ("channels", ctypes.c_int32), ("flags", ctypes.c_uint32)]
 
 
+# ABI 24: md2_depth_eval (csrc/eval.hip)
+EVAL_POST_PROCESS = 1 << 0
+EVAL_RESIZE_DEPTH = 1 << 1
+EVAL_GT_RANGE = 1 << 2
+EVAL_MEDIAN_SCALE = 1 << 3
+EVAL_MEDIAN_LOWER = 1 << 4
+EVAL_POOL_BATCH = 1 << 5
+EVAL_OUT = 10   # floats per population
+
+
+class EvalDesc(ctypes.Structure):
+    _fields_ = [("batch", ctypes.c_int32), ("height", ctypes.c_int32), ("width", ctypes.c_int32),
+                ("gt_height", ctypes.c_int32), ("gt_width", ctypes.c_int32),
+                ("crop_y0", ctypes.c_int32), ("crop_y1", ctypes.c_int32), ("crop_x0", ctypes.c_int32),
+                ("crop_x1", ctypes.c_int32), ("flags", ctypes.c_uint32),
+                ("min_depth", ctypes.c_double), ("max_depth", ctypes.c_double),
+                ("eval_min", ctypes.c_float), ("eval_max", ctypes.c_float),
+                ("scale_factor", ctypes.c_double)]
+
+
 def _declare(L):
+    L.md2_depth_eval_workspace_bytes.restype = ctypes.c_size_t
+    L.md2_depth_eval_workspace_bytes.argtypes = [ctypes.POINTER(EvalDesc)]
+    L.md2_depth_eval.restype = ctypes.c_int
+    L.md2_depth_eval.argtypes = [ctypes.POINTER(EvalDesc)] + [_vp] * 6
     L.md2_bias_act_fwd.restype = ctypes.c_int
     L.md2_bias_act_fwd.argtypes = [ctypes.POINTER(BiasActDesc)] + [_vp] * 4
     L.md2_bias_act_bwd.restype = ctypes.c_int

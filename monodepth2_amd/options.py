@@ -70,6 +70,8 @@ _FLAGS = [
     ("--eval_eigen_to_benchmark", dict(action="store_true", help="eigen npy evaluated on benchmark")),
     ("--eval_out_dir", dict(type=str, help="output folder for disparities")),
     ("--post_process", dict(action="store_true", help="flip post-processing")),
+    ("--gt_depths", dict(type=str, help="build: ground-truth .npz (key `data`) for evaluate_depth; default "
+                                        "splits/<eval_split>/gt_depths.npz beside the package")),
     # build-specific
     ("--materialize_images", dict(action="store_true",
                                   help="build: also materialise warped colours/samples/depth every step")),

@@ -33,6 +33,7 @@ import torch.optim as optim
 
 from . import conv_ops, networks
 from .distributed import FlatGradSync, wrap_ddp
+from .eval_ops import depth_metrics
 from .hotpath import HotPathConfig, generate_images, photometric_loss, predictive_mask_inputs, selection_maps
 from .bn_ops import bn_groups
 from .layers import compute_depth_errors, disp_to_depth
@@ -696,6 +697,29 @@ class Trainer:
         self.model_lr_scheduler.step()
         self.epoch += 1
         self._agree_conv_choices(again=True)
+
+    def val_step(self, inputs):
+        """One validation batch (trainer.py:211-226 val()): the networks in eval mode under
+        no_grad, the losses, and with inputs["depth_gt"] the seven depth metrics of
+        compute_depth_losses as device scalars from the fused evaluation kernel
+        (eval_ops.depth_metrics: the monitor formulation — depth resized to the ground
+        truth, Eigen crop, one torch.median-convention scaling over the whole batch).  No
+        host sync: the caller reads the values when it wants them.  Training state
+        (parameters, BatchNorm statistics, step counters) is left as it was."""
+        self.set_eval()
+        try:
+            with torch.no_grad():
+                outputs, losses = self.process_batch(inputs)
+                if "depth_gt" in inputs:
+                    # --amp bf16 leaves the disparities in bf16 (_to_fp32): widened exactly
+                    m = depth_metrics(outputs[("disp", 0)].float(), inputs["depth_gt"], mode="monitor", crop="eigen",
+                                      pool_batch=True, median_lower=True, min_depth=self.opt.min_depth,
+                                      max_depth=self.opt.max_depth)
+                    for i, name in enumerate(self.depth_metric_names):
+                        losses[name] = m[0, i]
+        finally:
+            self.set_train()
+        return outputs, losses
 
     def compute_depth_losses(self, inputs, outputs, losses):
         """trainer.py:498-526 (monitoring only)."""
