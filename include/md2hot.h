@@ -699,6 +699,56 @@ size_t md2_depth_eval_workspace_bytes(const md2_eval_desc* desc);
 int md2_depth_eval(const md2_eval_desc* desc, const float* disp, const float* disp_flipped, const float* gt,
                    float* out, void* workspace, void* stream);
 
+/*
+ * KITTI velodyne scans -> sparse ground-truth depth maps (csrc/velo.hip): the reference's
+ * kitti_utils.generate_depth_map (kitti_utils.py:46-98), which export_gt_depth.py and
+ * KITTIRAWDataset.get_depth run per frame in numpy and a Python loop, for a batch of
+ * frames of one image size as a fixed chain of launches on `stream` (memset, scatter,
+ * resolve).  Added under ABI 24 without raising MD2_ABI_VERSION: the additions are new
+ * symbols only, no existing struct or function changed, and md2_build_id already refuses
+ * a library built from other sources.
+ *
+ * points: fp32 (total_points, 4) rows x, y, z, reflectance, the frames' .bin contents
+ * concatenated (the fourth value is ignored); offsets: int64 (B + 1), frame b owns the
+ * rows offsets[b] .. offsets[b+1]; P: fp64 (B, 3, 4), P_rect_0{cam} @ R_rect_00 (4x4) @
+ * velo2cam (4x4) per frame; depth: fp32 (B, height, width), written completely (0 = no
+ * measurement).  All on the device.  Per frame, with the point order being the row order:
+ *   - a point is kept if x >= 0;
+ *   - q = P . (x, y, z, 1) in fp64, ((P0*x + P1*y) + P2*z) + P3 uncontracted;
+ *     u = rint(q0 / q2) - 1, v = rint(q1 / q2) - 1 (half to even); it is valid if
+ *     0 <= u < width and 0 <= v < height, compared in fp64 (NaN, infinite and q2 == 0
+ *     points fail the comparisons); its depth is q2, or x with MD2_VELO_VEL_DEPTH;
+ *   - every pixel first takes the depth of its last valid point;
+ *   - valid points are grouped by the reference's sub2ind key v * (width - 1) + u - 1,
+ *     which (v, width-1) and (v+1, 0) share; the pixel of a group's first point takes the
+ *     minimum depth of the group.  So a pixel with several points gets their minimum, and
+ *     of a wrapped pair one pixel gets the minimum over both while the other keeps its
+ *     last-written value;
+ *   - negative depths become 0; the map is rounded to fp32 (exact with VEL_DEPTH).
+ * Refused (MD2_ERR_ARG): NULL operands, non-positive sizes, width < 2 (the key
+ * degenerates), batch > 65535, batch * height * width or total_points at or above 2^31.
+ * The offsets cannot be checked without a synchronisation: 0 = offsets[0] <= ... <=
+ * offsets[B] = total_points is the caller's contract (rows outside [0, total_points) are
+ * never read, the maps of a broken table are meaningless).
+ * workspace: the size the function below returns, no initialisation needed, 16 bytes per
+ * pixel.  Integer atomics only: bitwise repeatable for any arrival order, any number of
+ * points per pixel.  hipGraph-capturable, no allocation, no host synchronisation.
+ */
+#define MD2_VELO_VEL_DEPTH (1u << 0)   /* the depth of a point is its own x (export_gt_depth.py:49) */
+
+typedef struct md2_velo_desc {
+    int32_t batch;                  /* B frames */
+    int32_t height, width;          /* of every map of the call (S_rect_02 reversed) */
+    uint32_t flags;                 /* MD2_VELO_* */
+    int64_t total_points;           /* rows of points (offset 16) */
+    int32_t reserved[2];            /* 0; the struct is 32 bytes */
+} md2_velo_desc;
+
+/* 0 (and md2_last_error) for a desc md2_velo_project would refuse */
+size_t md2_velo_project_workspace_bytes(const md2_velo_desc* desc);
+int md2_velo_project(const md2_velo_desc* desc, const float* points, const int64_t* offsets, const double* P,
+                     float* depth, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -70,7 +70,8 @@ EXPORTS = ["md2_abi_version", "md2_last_error", "md2_workspace_bytes", "md2_sele
            "md2_conv_wgrad_direct_workspace_bytes", "md2_conv_split_weights_multi", "md2_bn_fwd_mask",
            "md2_bn_bwd_mask", "md2_build_id", "md2_maxpool3s2_bwd_multi", "md2_decoder_pad_bwd2", "md2_aug_run2",
            "md2_conv_bf16_weights", "md2_conv_bf16_weights_multi",
-           "md2_depth_eval", "md2_depth_eval_workspace_bytes"]
+           "md2_depth_eval", "md2_depth_eval_workspace_bytes",
+           "md2_velo_project", "md2_velo_project_workspace_bytes"]
 
 DTYPE_F32 = 0    # md2_desc.disp_dtype
 DTYPE_BF16 = 1
@@ -187,7 +188,20 @@ class EvalDesc(ctypes.Structure):
                 ("scale_factor", ctypes.c_double)]
 
 
+# md2_velo_project (csrc/velo.hip): new symbols under ABI 24, no version bump
+VELO_VEL_DEPTH = 1 << 0
+
+
+class VeloDesc(ctypes.Structure):
+    _fields_ = [("batch", ctypes.c_int32), ("height", ctypes.c_int32), ("width", ctypes.c_int32),
+                ("flags", ctypes.c_uint32), ("total_points", ctypes.c_int64), ("reserved", ctypes.c_int32 * 2)]
+
+
 def _declare(L):
+    L.md2_velo_project_workspace_bytes.restype = ctypes.c_size_t
+    L.md2_velo_project_workspace_bytes.argtypes = [ctypes.POINTER(VeloDesc)]
+    L.md2_velo_project.restype = ctypes.c_int
+    L.md2_velo_project.argtypes = [ctypes.POINTER(VeloDesc)] + [_vp] * 6
     L.md2_depth_eval_workspace_bytes.restype = ctypes.c_size_t
     L.md2_depth_eval_workspace_bytes.argtypes = [ctypes.POINTER(EvalDesc)]
     L.md2_depth_eval.restype = ctypes.c_int

@@ -12,8 +12,12 @@ package, where the reference keeps it).  The per-image loop of evaluate_depth.py
 HIP operator of `eval_ops.depth_metrics`, one call per group of equally sized
 ground-truth maps, and prints the reference's result table.
 
+The ground-truth file comes from `python -m monodepth2_amd.export_gt_depth` (velodyne
+scans projected by csrc/velo.hip); `evaluate_from_velodyne` skips the file and evaluates
+against maps projected on the device.
+
 Out of scope here, refused with a clear error instead of half-working: loading KITTI
-frames from --data_path (this tree has no dataset readers, so predictions come from
+images from --data_path (this tree decodes no JPEGs, so predictions come from
 --ext_disp_to_eval, or from `predict_disparities` on images the caller loaded), the
 `benchmark` split's 16-bit PNG export (no cv2), and --eval_eigen_to_benchmark (needs the
 reference's id table).  Images for `predict_disparities` are (N,3,H,W) in [0,1].
@@ -79,7 +83,9 @@ def post_process_disparity(l_disp: torch.Tensor, r_disp: torch.Tensor) -> torch.
 def evaluate_disparities(pred_disps, gt_depths: Sequence, opt, pred_disps_flipped=None,
                          device=None, scaled: bool = False) -> Dict[str, object]:
     """evaluate_depth.py:170-221 on raw sigmoid disparities (N,h,w) or (N,1,h,w) (numpy or
-    torch) against N ground-truth maps (arrays, possibly of different sizes).  `scaled`:
+    torch) against N ground-truth maps (host arrays, possibly of different sizes; or maps
+    already on the device, as a (N,GH,GW) tensor or a list of device tensors, which are
+    then neither stacked on the host nor uploaded).  `scaled`:
     the disparities already went through disp_to_depth (what the reference's
     --save_pred_disps files hold).  Images are
     grouped by ground-truth shape, each group is one depth_metrics call; one device-to-host
@@ -103,13 +109,27 @@ def evaluate_disparities(pred_disps, gt_depths: Sequence, opt, pred_disps_flippe
 
     disp = to_dev(pred_disps)
     flipped = to_dev(pred_disps_flipped) if pred_disps_flipped is not None else None
+    # ground truth born on the device (kitti_utils.generate_depth_maps) stays there: a
+    # (N,GH,GW) tensor is one group as it is, device maps of a list are stacked on the device
+    whole = torch.is_tensor(gt_depths) and gt_depths.is_cuda and gt_depths.dim() == 3
     groups: Dict[tuple, List[int]] = {}
-    for i, g in enumerate(gt_depths):
-        groups.setdefault(tuple(g.shape[:2]), []).append(i)
+    if whole:
+        groups[tuple(gt_depths.shape[1:])] = list(range(n))
+    else:
+        for i, g in enumerate(gt_depths):
+            groups.setdefault(tuple(g.shape[:2]), []).append(i)
     results = torch.empty((n, 10), dtype=torch.float32, device=device)
+
+    def gt_of(idx):
+        if whole:
+            return gt_depths.to(device=device, dtype=torch.float32)
+        if all(torch.is_tensor(gt_depths[i]) and gt_depths[i].is_cuda for i in idx):
+            return torch.stack([gt_depths[i] for i in idx]).to(device=device, dtype=torch.float32)
+        return torch.stack([torch.as_tensor(np.asarray(gt_depths[i], dtype=np.float32)) for i in idx]).to(device)
+
     for shape, idx in groups.items():
         sel = torch.as_tensor(idx, device=device)
-        gt = torch.stack([torch.as_tensor(np.asarray(gt_depths[i], dtype=np.float32)) for i in idx]).to(device)
+        gt = gt_of(idx)
         out = depth_metrics(disp[sel], gt, mode="evaluate",
                             post_process_disp=flipped[sel] if flipped is not None else None,
                             median_scaling=median_scaling, scale_factor=scale_factor,
@@ -125,6 +145,18 @@ def evaluate_disparities(pred_disps, gt_depths: Sequence, opt, pred_disps_flippe
         med = np.median(ratios)
         out.update(ratios=ratios, ratio_median=med, ratio_std=np.std(ratios / med))
     return out
+
+
+def evaluate_from_velodyne(pred_disps, frames, opt, pred_disps_flipped=None, device=None, scaled: bool = False,
+                           cam: int = 2, vel_depth: bool = True) -> Dict[str, object]:
+    """`evaluate_disparities` against ground truth projected here from the velodyne scans
+    `frames`, a sequence of (calib_dir, velo_filename): kitti_utils.generate_depth_maps
+    (csrc/velo.hip) leaves the maps on the device and depth_metrics reads them there.  The
+    defaults are export_gt_depth.py's (camera 2, the points' own forward distance)."""
+    from .kitti_utils import generate_depth_maps
+    device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    gt = generate_depth_maps(frames, cam=cam, vel_depth=vel_depth, device=device)
+    return evaluate_disparities(pred_disps, gt, opt, pred_disps_flipped, device, scaled=scaled)
 
 
 def format_results(res) -> str:
