@@ -749,6 +749,60 @@ size_t md2_velo_project_workspace_bytes(const md2_velo_desc* desc);
 int md2_velo_project(const md2_velo_desc* desc, const float* points, const int64_t* offsets, const double* P,
                      float* depth, void* workspace, void* stream);
 
+/*
+ * KITTI odometry pose evaluation (csrc/traj.hip): the reference's evaluate_pose.py:104-125
+ * — local ground-truth poses, 5-frame snippets, scale-aligned absolute trajectory error
+ * (ATE), mean and standard deviation — for a batch of sequences as a fixed chain of three
+ * launches on `stream` (local poses, errors, statistics), every step in fp64.  New
+ * symbols under ABI 24, no version bump (as md2_velo_project).
+ *
+ * Sequence s owns the frames offsets[s] .. offsets[s+1] (M_s of them) of gt, fp64
+ * (total_frames, 3, 4) KITTI pose rows; its M_s - 1 predicted transforms start at row
+ * offsets[s] - s of pred, fp32 (total_frames - S, 4, 4), what the reference stores in
+ * poses.npy (transformation_from_parameters(axisangle[:, 0], translation[:, 0]), not
+ * inverted); its errors start at the same row of ates, fp64 (total_frames - S); stats is
+ * fp64 (S, 2): mean, population standard deviation.  All on the device.
+ *   - G_i is the 3x4 block over [0,0,0,1]; L_i = inv(inv(G_{i-1}) . G_i), i = 1..M_s-1,
+ *     literally: two inverses and a product.  The inverse is the general affine one,
+ *     cofactors of the 3x3 over det = (a00*c00 + a01*c01) + a02*c02, then
+ *     -((i0*t0 + i1*t1) + i2*t2) per row — not [R^T | -R^T t], which is 1e-7..1e-6 off on
+ *     KITTI's seven-digit rotations far from the origin;
+ *   - a product is ((a0*b0 + a1*b1) + a2*b2) + a3*b3 per element, the bottom row of the
+ *     right factor included ([0,0,0,1] for L, the stored row of a prediction);
+ *   - snippet i (0 <= i < M_s - 1) chains n = min(track_length - 1, M_s - 1 - i)
+ *     transforms from C = I, C = C . T_k, a point being C[:3, 3] after each, the first
+ *     (0,0,0): n + 1 points from L and n + 1 from pred (fp32 promoted to fp64);
+ *   - offset = gt[0] - pred[0], pred += offset; num = sum gt*pred, den = sum pred*pred
+ *     (points in order, x, y, z within a point, from 0.0); scale = num / den;
+ *     ate = sqrt(sum (pred*scale - gt)^2) / (n + 1).  All-zero predicted points give
+ *     0/0 = nan, as in the reference;
+ *   - mean = sum(ates) / (M_s-1), std = sqrt(sum((a - mean)^2) / (M_s-1)); both sums have
+ *     a fixed shape: 256 lanes, lane j adds elements j, j+256, ... in rising order from
+ *     0.0, then strides 128, 64, ..., 1 fold lane j+stride into lane j.
+ * No contraction anywhere, no float atomics: bitwise repeatable, independent of the
+ * launch geometry.  hipGraph-capturable, no allocation, no host synchronisation.
+ * Refused (MD2_ERR_ARG): NULL desc or operand, sequences < 1 or > 65535, track_length
+ * outside 2..16, non-zero flags, total_frames < 2 * sequences or >= 2^31, a workspace
+ * not 256-byte aligned.  The offsets cannot be checked without a synchronisation:
+ * 0 = offsets[0] <= ... <= offsets[S] = total_frames with at least two frames per
+ * sequence is the caller's contract.  A sequence found shorter than two frames (or whose
+ * rows would leave the operands) gets nan in its stats row and nothing else is written
+ * for it.  workspace: the size the query returns (the local poses), no initialisation.
+ */
+typedef struct md2_pose_ate_desc {
+    int32_t sequences;              /* S >= 1 */
+    int32_t track_length;           /* points per snippet, 2..16; the reference uses 5 */
+    uint32_t flags;                 /* none defined yet: non-zero is refused */
+    int32_t reserved0;
+    int64_t total_frames;           /* sum of ground-truth frames over all sequences (offset 16) */
+    int64_t reserved;               /* 0; the struct is 32 bytes */
+} md2_pose_ate_desc;
+
+/* 0 (and md2_last_error) for a desc md2_pose_ate would refuse */
+size_t md2_pose_ate_workspace_bytes(const md2_pose_ate_desc* desc);
+int md2_pose_ate(const md2_pose_ate_desc* desc, const float* pred, const double* gt, const int64_t* offsets,
+                 double* ates, double* stats, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -71,7 +71,8 @@ EXPORTS = ["md2_abi_version", "md2_last_error", "md2_workspace_bytes", "md2_sele
            "md2_bn_bwd_mask", "md2_build_id", "md2_maxpool3s2_bwd_multi", "md2_decoder_pad_bwd2", "md2_aug_run2",
            "md2_conv_bf16_weights", "md2_conv_bf16_weights_multi",
            "md2_depth_eval", "md2_depth_eval_workspace_bytes",
-           "md2_velo_project", "md2_velo_project_workspace_bytes"]
+           "md2_velo_project", "md2_velo_project_workspace_bytes",
+           "md2_pose_ate", "md2_pose_ate_workspace_bytes"]
 
 DTYPE_F32 = 0    # md2_desc.disp_dtype
 DTYPE_BF16 = 1
@@ -197,7 +198,17 @@ class VeloDesc(ctypes.Structure):
                 ("flags", ctypes.c_uint32), ("total_points", ctypes.c_int64), ("reserved", ctypes.c_int32 * 2)]
 
 
+# md2_pose_ate (csrc/traj.hip): new symbols under ABI 24, no version bump
+class PoseAteDesc(ctypes.Structure):
+    _fields_ = [("sequences", ctypes.c_int32), ("track_length", ctypes.c_int32), ("flags", ctypes.c_uint32),
+                ("reserved0", ctypes.c_int32), ("total_frames", ctypes.c_int64), ("reserved", ctypes.c_int64)]
+
+
 def _declare(L):
+    L.md2_pose_ate_workspace_bytes.restype = ctypes.c_size_t
+    L.md2_pose_ate_workspace_bytes.argtypes = [ctypes.POINTER(PoseAteDesc)]
+    L.md2_pose_ate.restype = ctypes.c_int
+    L.md2_pose_ate.argtypes = [ctypes.POINTER(PoseAteDesc)] + [_vp] * 7
     L.md2_velo_project_workspace_bytes.restype = ctypes.c_size_t
     L.md2_velo_project_workspace_bytes.argtypes = [ctypes.POINTER(VeloDesc)]
     L.md2_velo_project.restype = ctypes.c_int

@@ -72,6 +72,9 @@ _FLAGS = [
     ("--post_process", dict(action="store_true", help="flip post-processing")),
     ("--gt_depths", dict(type=str, help="build: ground-truth .npz (key `data`) for evaluate_depth; default "
                                         "splits/<eval_split>/gt_depths.npz beside the package")),
+    ("--gt_poses", dict(type=str, help="build: KITTI poses file (12 numbers per line) for evaluate_pose; default "
+                                       "<data_path>/poses/NN.txt")),
+    ("--ext_poses_to_eval", dict(type=str, help="build: external poses.npy (N,4,4) float32 for evaluate_pose")),
     # build-specific
     ("--materialize_images", dict(action="store_true",
                                   help="build: also materialise warped colours/samples/depth every step")),
