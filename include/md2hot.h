@@ -803,6 +803,53 @@ size_t md2_pose_ate_workspace_bytes(const md2_pose_ate_desc* desc);
 int md2_pose_ate(const md2_pose_ate_desc* desc, const float* pred, const double* gt, const int64_t* offsets,
                  double* ates, double* stats, void* workspace, void* stream);
 
+/*
+ * Disparity -> colour picture (csrc/viz.hip): the tail of the reference's test_simple.py
+ * (136-155) — bilinear resize to the original image size, np.percentile(., 95) and .min(),
+ * matplotlib's Normalize and `magma`, uint8 — for a batch of equally sized maps as a fixed
+ * chain of launches on `stream` (memset, resize, four radix-select passes, finalise,
+ * colourise).  New symbols under ABI 24, no version bump (as md2_pose_ate).
+ *
+ * disp: fp32 (B, 1, in_height, in_width) contiguous; rgb: uint8 (B, H, W, 3), row stride
+ * 3 * W bytes; resized (optional, may be NULL): fp32 (B, H, W); stats (optional): fp32
+ * (B, 2), vmin and vmax per image.  All on the device; statistics are per image.
+ *   - resize, fp32, F.interpolate(bilinear, align_corners=False): s = f32(in) / f32(out),
+ *     src = max(s * (dst + 0.5f) - 0.5f, 0), i0 = (int)src, i1 = min(i0 + 1, in - 1),
+ *     l1 = src - i0, l0 = 1 - l1, r = hy0 * (wx0*a + wx1*b) + hy1 * (wx0*c + wx1*d); at
+ *     equal sizes r is the input (a -0 becomes +0, a NaN or infinity spreads to the
+ *     neighbours whose zero weight multiplies it);
+ *   - with n = H * W and a[0..n-1] the sorted map: q = f32(percentile) / 100f,
+ *     vi = f32(n-1) * q; vi >= n-1: vmax = a[n-1]; else lo = floor(vi), g = vi - lo,
+ *     d = a[lo+1] - a[lo], vmax = g >= 0.5 ? a[lo+1] - d * (1 - g) : a[lo] + d * g, all
+ *     fp32 (numpy's `linear` method on an fp32 array); vmin = min(r), -0 below +0;
+ *   - vmin == vmax: t = 0; else u = f32(f64(r) - f64(vmin)),
+ *     t = f32(f64(u) / (f64(vmax) - f64(vmin))); x = t * 256f; index 0 if x < 0 or x is
+ *     NaN, 255 if x >= 256, else (int)x; the pixel is entry `index` of matplotlib's magma
+ *     table as (uint8)(channel * 255);
+ *   - a map that holds a NaN after the resize: every pixel (0, 0, 0), vmin = vmax = NaN.
+ *     Infinities index inside the table; what they select is unspecified.
+ * No contraction, integer atomics only: bitwise repeatable.  hipGraph-capturable, no
+ * allocation, no host synchronisation.
+ * Refused (MD2_ERR_ARG): NULL desc, disp, rgb or workspace, a non-positive size, batch >
+ * 65535, out_height * out_width > 2^24 (f32(n-1) must be exact), in_height * in_width >=
+ * 2^31, a percentile outside 0..100, non-zero flags, a workspace not 256-byte aligned.
+ * workspace: the size the query returns (the resized maps, histograms, partials), no
+ * initialisation needed.
+ */
+typedef struct md2_viz_desc {
+    int32_t batch;                  /* B images, 1..65535 */
+    int32_t in_height, in_width;    /* of disp */
+    int32_t out_height, out_width;  /* H, W of the picture */
+    int32_t percentile;             /* 0..100; the reference uses 95 */
+    uint32_t flags;                 /* none defined yet: non-zero is refused */
+    int32_t reserved;               /* 0; the struct is 32 bytes */
+} md2_viz_desc;
+
+/* 0 (and md2_last_error) for a desc md2_disp_colorize would refuse */
+size_t md2_disp_colorize_workspace_bytes(const md2_viz_desc* desc);
+int md2_disp_colorize(const md2_viz_desc* desc, const float* disp, uint8_t* rgb, float* resized, float* stats,
+                      void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

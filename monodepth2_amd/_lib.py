@@ -72,7 +72,8 @@ EXPORTS = ["md2_abi_version", "md2_last_error", "md2_workspace_bytes", "md2_sele
            "md2_conv_bf16_weights", "md2_conv_bf16_weights_multi",
            "md2_depth_eval", "md2_depth_eval_workspace_bytes",
            "md2_velo_project", "md2_velo_project_workspace_bytes",
-           "md2_pose_ate", "md2_pose_ate_workspace_bytes"]
+           "md2_pose_ate", "md2_pose_ate_workspace_bytes",
+           "md2_disp_colorize", "md2_disp_colorize_workspace_bytes"]
 
 DTYPE_F32 = 0    # md2_desc.disp_dtype
 DTYPE_BF16 = 1
@@ -204,7 +205,18 @@ class PoseAteDesc(ctypes.Structure):
                 ("reserved0", ctypes.c_int32), ("total_frames", ctypes.c_int64), ("reserved", ctypes.c_int64)]
 
 
+# md2_disp_colorize (csrc/viz.hip): new symbols under ABI 24, no version bump
+class VizDesc(ctypes.Structure):
+    _fields_ = [("batch", ctypes.c_int32), ("in_height", ctypes.c_int32), ("in_width", ctypes.c_int32),
+                ("out_height", ctypes.c_int32), ("out_width", ctypes.c_int32), ("percentile", ctypes.c_int32),
+                ("flags", ctypes.c_uint32), ("reserved", ctypes.c_int32)]
+
+
 def _declare(L):
+    L.md2_disp_colorize_workspace_bytes.restype = ctypes.c_size_t
+    L.md2_disp_colorize_workspace_bytes.argtypes = [ctypes.POINTER(VizDesc)]
+    L.md2_disp_colorize.restype = ctypes.c_int
+    L.md2_disp_colorize.argtypes = [ctypes.POINTER(VizDesc)] + [_vp] * 6
     L.md2_pose_ate_workspace_bytes.restype = ctypes.c_size_t
     L.md2_pose_ate_workspace_bytes.argtypes = [ctypes.POINTER(PoseAteDesc)]
     L.md2_pose_ate.restype = ctypes.c_int
