@@ -269,6 +269,10 @@ int md2_disp_head_bwd(const md2_head_desc* desc, const float* padded, const floa
  * fp32); md2_stem_fwd's x and y (the fp32 weight rounded to bf16, fp32 accumulation,
  * y rounded to nearest even) */
 #define MD2_STEM_BF16 (1u << 1)
+/* md2_stem_wgrad / md2_stem_wgrad_bn, fp32, channels 3 / 6: this call runs the form that
+ * prefetches the next chunk behind the MFMAs (what MD2_STEM_PF32=1 selects for every
+ * call); same sums, bit for bit */
+#define MD2_STEM_PREFETCH (1u << 2)
 
 typedef struct md2_stem_desc {
     int32_t batch, channels, height, width; /* of the input */
@@ -849,6 +853,44 @@ typedef struct md2_viz_desc {
 size_t md2_disp_colorize_workspace_bytes(const md2_viz_desc* desc);
 int md2_disp_colorize(const md2_viz_desc* desc, const float* disp, uint8_t* rgb, float* resized, float* stats,
                       void* workspace, void* stream);
+
+/*
+ * The ResNet stem's BatchNorm elementwise passes folded into their neighbours
+ * (csrc/bnorm.hip, csrc/stem.hip; networks/resnet_encoder.py:62-98 conv1 -> bn1 -> relu ->
+ * maxpool).  New symbols under ABI 24, no version bump (as md2_disp_colorize).  Every
+ * output is bit for bit what the unfused launches give; all calls are hipGraph-capturable
+ * (no allocation, no host synchronisation).
+ *
+ * md2_bn_pool_fwd = md2_bn_fwd_mask (statistics and finaliser launches unchanged) whose
+ * apply pass also is md2_maxpool3s2_fwd: it reads x once and writes the pooled map
+ * (batch, height/2, width/2, channels), the pool's idx words, relu_mask, and y only when y
+ * is not NULL (a caller that uses the pooled map alone never materialises y).
+ * desc->pixels = batch * height * width.  Takes fp32, MD2_BN_RELU alone, even height and
+ * width, batch * height / 2 <= 65535 (md2_bn_pool_fwd_supported: 1 / 0); anything else is
+ * refused and runs as the two calls.
+ *
+ * md2_bn_bwd_reduce_mask = md2_bn_bwd_mask without its last launch: grad_gamma,
+ * grad_beta, and the three dx coefficient rows coef[3][groups][channels] (γ·invstd,
+ * Σg'/N, Σg'x̂/N·invstd) left in the workspace at byte offset md2_bn_coef_offset(desc).
+ * md2_stem_wgrad_bn = md2_stem_wgrad whose grad_y is that BatchNorm's missing dx, formed
+ * on load from grad (the gradient of relu(bn(z))), z, relu_mask, save_mean and coef in
+ * md2_bn_bwd_mask's expressions — dx is never written.  It must follow its
+ * md2_bn_bwd_reduce_mask on the same stream with no other BatchNorm call on that
+ * workspace in between.  fp32, channels 3 / 6 (md2_stem_wgrad_bn_supported: 1 / 0).
+ */
+int md2_bn_pool_fwd_supported(const md2_bn_desc* desc, int height, int width);
+int md2_bn_pool_fwd(const md2_bn_desc* desc, int height, int width, const float* x, const float* gamma,
+                    const float* beta, float* running_mean, float* running_var, float* y, uint8_t* relu_mask,
+                    float* pooled, uint32_t* idx, float* save_mean, float* save_invstd, void* workspace,
+                    void* stream);
+int md2_bn_bwd_reduce_mask(const md2_bn_desc* desc, const void* x, const uint8_t* relu_mask, const void* grad_y,
+                           const float* gamma, const float* save_mean, const float* save_invstd, float* grad_gamma,
+                           float* grad_beta, void* workspace, void* stream);
+size_t md2_bn_coef_offset(const md2_bn_desc* desc);
+int md2_stem_wgrad_bn_supported(const md2_stem_desc* desc);
+int md2_stem_wgrad_bn(const md2_stem_desc* desc, const float* x, const float* grad, const float* z,
+                      const uint8_t* relu_mask, const float* save_mean, const float* coef, int bn_groups,
+                      float* grad_weight, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }

@@ -73,7 +73,9 @@ EXPORTS = ["md2_abi_version", "md2_last_error", "md2_workspace_bytes", "md2_sele
            "md2_depth_eval", "md2_depth_eval_workspace_bytes",
            "md2_velo_project", "md2_velo_project_workspace_bytes",
            "md2_pose_ate", "md2_pose_ate_workspace_bytes",
-           "md2_disp_colorize", "md2_disp_colorize_workspace_bytes"]
+           "md2_disp_colorize", "md2_disp_colorize_workspace_bytes",
+           "md2_bn_pool_fwd_supported", "md2_bn_pool_fwd", "md2_bn_bwd_reduce_mask", "md2_bn_coef_offset",
+           "md2_stem_wgrad_bn_supported", "md2_stem_wgrad_bn"]
 
 DTYPE_F32 = 0    # md2_desc.disp_dtype
 DTYPE_BF16 = 1
@@ -156,6 +158,7 @@ class HeadDesc(ctypes.Structure):
 
 STEM_WEIGHT_CL = 1 << 0
 STEM_BF16 = 1 << 1   # ABI 23: md2_stem_wgrad on bf16 x / grad_y
+STEM_PREFETCH = 1 << 2   # the fp32 weight gradient's prefetching form for this call (MD2_STEM_PF32=1: every call)
 
 
 class StemDesc(ctypes.Structure):
@@ -213,6 +216,19 @@ class VizDesc(ctypes.Structure):
 
 
 def _declare(L):
+    # the stem's fused BatchNorm passes: new symbols under ABI 24, no version bump
+    L.md2_bn_pool_fwd_supported.restype = ctypes.c_int
+    L.md2_bn_pool_fwd_supported.argtypes = [ctypes.POINTER(BnDesc), ctypes.c_int, ctypes.c_int]
+    L.md2_bn_pool_fwd.restype = ctypes.c_int
+    L.md2_bn_pool_fwd.argtypes = [ctypes.POINTER(BnDesc), ctypes.c_int, ctypes.c_int] + [_vp] * 13
+    L.md2_bn_bwd_reduce_mask.restype = ctypes.c_int
+    L.md2_bn_bwd_reduce_mask.argtypes = [ctypes.POINTER(BnDesc)] + [_vp] * 10
+    L.md2_bn_coef_offset.restype = ctypes.c_size_t
+    L.md2_bn_coef_offset.argtypes = [ctypes.POINTER(BnDesc)]
+    L.md2_stem_wgrad_bn_supported.restype = ctypes.c_int
+    L.md2_stem_wgrad_bn_supported.argtypes = [ctypes.POINTER(StemDesc)]
+    L.md2_stem_wgrad_bn.restype = ctypes.c_int
+    L.md2_stem_wgrad_bn.argtypes = [ctypes.POINTER(StemDesc)] + [_vp] * 6 + [ctypes.c_int] + [_vp] * 3
     L.md2_disp_colorize_workspace_bytes.restype = ctypes.c_size_t
     L.md2_disp_colorize_workspace_bytes.argtypes = [ctypes.POINTER(VizDesc)]
     L.md2_disp_colorize.restype = ctypes.c_int

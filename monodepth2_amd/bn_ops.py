@@ -229,11 +229,15 @@ class _MaxPool(torch.autograd.Function):
         return gx, None, None
 
 
+def _pool_geometry_ok(pool: nn.MaxPool2d) -> bool:
+    """MaxPool2d(3, 2, 1), the ResNet stem's (also asked by stem_ops.stem_bn_pool)."""
+    return (pool.kernel_size in (3, (3, 3)) and pool.stride in (2, (2, 2)) and pool.padding in (1, (1, 1))
+            and pool.dilation in (1, (1, 1)) and not pool.ceil_mode and not pool.return_indices)
+
+
 def _pool_ok(pool: nn.MaxPool2d, x: torch.Tensor) -> bool:
     return (ENABLED and x.is_cuda and x.dim() == 4 and x.dtype in (torch.float32, torch.bfloat16)
-            and x.shape[1] % 4 == 0 and x.is_contiguous(memory_format=_CL)
-            and pool.kernel_size in (3, (3, 3)) and pool.stride in (2, (2, 2)) and pool.padding in (1, (1, 1))
-            and pool.dilation in (1, (1, 1)) and not pool.ceil_mode and not pool.return_indices)
+            and x.shape[1] % 4 == 0 and x.is_contiguous(memory_format=_CL) and _pool_geometry_ok(pool))
 
 
 def max_pool_3x3s2(pool: nn.MaxPool2d, x: torch.Tensor) -> torch.Tensor:

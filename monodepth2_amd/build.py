@@ -18,6 +18,7 @@ INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB_NAME = "libmd2hot.so"
 LIB_PATH = os.path.join(CSRC, LIB_NAME)
 SOURCES = ["md2hot.hip", "decoder.hip", "pose.hip", "augment.hip", "bnorm.hip", "pool.hip", "adam.hip", "disphead.hip", "stem.hip", "bias_act.hip", "conv.hip", "direct.hip", "glue.hip", "eval.hip", "velo.hip", "traj.hip", "viz.hip"]
+HEADERS = [os.path.join(INCLUDE, "md2hot.h"), os.path.join(CSRC, "md2_bf16.h"), os.path.join(CSRC, "md2_bn_expr.h")]
 ARCH = os.environ.get("MD2_OFFLOAD_ARCH", "gfx950")
 
 
@@ -32,8 +33,7 @@ def needs_build() -> bool:
     if not os.path.exists(LIB_PATH):
         return True
     t = os.path.getmtime(LIB_PATH)
-    deps = [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(INCLUDE, "md2hot.h"),
-                                                       os.path.join(CSRC, "md2_bf16.h")]
+    deps = [os.path.join(CSRC, s) for s in SOURCES] + HEADERS
     if any(os.path.getmtime(d) > t for d in deps):
         return True
     # per-source flags changed (they are part of the build id, not of any mtime).  The
@@ -90,8 +90,7 @@ def source_hash() -> str:
     flags, target architecture): baked into the library as md2_build_id() and checked
     against the tree by _lib.lib(), so a stale prebuilt .so cannot load silently."""
     h = hashlib.sha256()
-    for path in [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(INCLUDE, "md2hot.h"),
-                                                          os.path.join(CSRC, "md2_bf16.h")]:
+    for path in [os.path.join(CSRC, s) for s in SOURCES] + HEADERS:
         h.update(os.path.basename(path).encode())
         with open(path, "rb") as f:
             h.update(f.read())

@@ -20,6 +20,11 @@
 // ~15 µs per layer on this chip: device-scope fences + ticket atomic + the finalising
 // block's reads of the partials from memory form a serial chain.)
 //
+// The ResNet stem (md2_bn_pool_fwd, md2_bn_bwd_reduce_mask): its apply pass also is the
+// max-pool that follows it (bn_relu_pool_kernel: one pass over the step's largest
+// activation instead of a write and two reads), and its backward stops after the
+// reductions — stem.hip's weight gradient forms dx from the coefficient rows on load.
+//
 // Layout: x, y, r, g, dx, dr (N·H·W, C) fp32 — a channels_last NCHW tensor; C a
 // multiple of 4 (every ResNet width is).  Deterministic: fixed-order reductions, no
 // atomics.
@@ -30,6 +35,7 @@
 #include <stdlib.h>
 
 #include "md2_bf16.h"
+#include "md2_bn_expr.h"
 #include "md2hot.h"
 
 int md2_report_error(int code, const char* msg);
@@ -233,18 +239,12 @@ __global__ void __launch_bounds__(kThreads) bn_apply_kernel(const void* __restri
         const int c = 4 * (j & (Q - 1));
         const float4 v = ldT<T>(x, 4 * i), mu = ld4(mug + c), is = ld4(isg + c), ga = ld4(gamma + c),
                      be = ld4(beta + c);
-        float4 o;
-        o.x = (v.x - mu.x) * is.x * ga.x + be.x;
-        o.y = (v.y - mu.y) * is.y * ga.y + be.y;
-        o.z = (v.z - mu.z) * is.z * ga.z + be.z;
-        o.w = (v.w - mu.w) * is.w * ga.w + be.w;
+        float4 o = md2::bn_affine4(v, mu, is, ga, be);
         if (RES) {
             const float4 rv = ldT<T>(r, 4 * i);
             o.x += rv.x; o.y += rv.y; o.z += rv.z; o.w += rv.w;
         }
-        if (RELU) {
-            o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
-        }
+        if (RELU) o = md2::relu4(o);
         stT<T>(y, 4 * i, o);
         if (MOUT)
             mask[i] = (uint8_t)((stored_pos<T>(o.x) ? 1 : 0) | (stored_pos<T>(o.y) ? 2 : 0) |
@@ -256,8 +256,7 @@ __global__ void __launch_bounds__(kThreads) bn_apply_kernel(const void* __restri
 template <typename T, bool MIN>
 __device__ __forceinline__ float4 relu_gate(const void* y, size_t off, float4 g) {
     if constexpr (MIN) {
-        const uint32_t m = ((const uint8_t*)y)[off >> 2];
-        g.x = (m & 1) ? g.x : 0.f; g.y = (m & 2) ? g.y : 0.f; g.z = (m & 4) ? g.z : 0.f; g.w = (m & 8) ? g.w : 0.f;
+        g = md2::relu_gate_mask4(y, off, g);
     } else {
         const float4 yv = ldT<T>(y, off);
         g.x = yv.x > 0.f ? g.x : 0.f; g.y = yv.y > 0.f ? g.y : 0.f;
@@ -371,11 +370,7 @@ __global__ void __launch_bounds__(kThreads) bn_bwd_apply_kernel(const void* __re
         if (RELU) gv = relu_gate<T, MIN>(y, 4 * i, gv);
         const float4 v = ldT<T>(x, 4 * i), mu = ld4(smean + c), k1 = ld4(coef + c),
                      k2 = ld4(coef + (size_t)NG * C + c), k3 = ld4(coef + 2 * (size_t)NG * C + c);
-        float4 o;
-        o.x = k1.x * (gv.x - k2.x - (v.x - mu.x) * k3.x);
-        o.y = k1.y * (gv.y - k2.y - (v.y - mu.y) * k3.y);
-        o.z = k1.z * (gv.z - k2.z - (v.z - mu.z) * k3.z);
-        o.w = k1.w * (gv.w - k2.w - (v.w - mu.w) * k3.w);
+        const float4 o = md2::bn_bwd_dx4(gv, v, mu, k1, k2, k3);
         stT<T>(dx, 4 * i, o);
         if (RES) stT<T>(dr, 4 * i, gv);
     }
@@ -633,10 +628,70 @@ bool valid(const md2_bn_desc* d) {
     return Q >= kThreads ? (Q % kThreads == 0) : (kThreads % Q == 0);
 }
 
+// The stem's BatchNorm apply + ReLU + MaxPool2d(3, 2, 1) in one pass over z (fp32, even
+// H and W): one thread per (image, output pixel, channel quad) evaluates its nine window
+// activations with bn_apply_kernel's expression, takes the max by maxpool_fwd_kernel's
+// rules (md2_bn_expr.h), and stores y (YOUT) and the ReLU mask for the 2x2 input pixels
+// (2 oy + {0,1}, 2 ox + {0,1}) — window taps 4, 5, 7, 8 — so every input pixel is stored
+// once.  Without YOUT (the pose encoder: only the pooled map is used) y never exists;
+// with it the pool no longer reads y back.  blockIdx.y = b·Ho + oy; the BatchNorm group
+// is the image's batch chunk.
+struct StemPoolGeom {
+    int B, H, W, Ho, Wo;
+    int ipg;   // images per BatchNorm group
+};
+
+template <bool YOUT>
+__global__ void __launch_bounds__(kThreads) bn_relu_pool_kernel(StemPoolGeom p, int q_shift,
+                                                                const float* __restrict__ z,
+                                                                const float* __restrict__ gamma,
+                                                                const float* __restrict__ beta,
+                                                                const float* __restrict__ smean,
+                                                                const float* __restrict__ sinvstd,
+                                                                float* __restrict__ y, uint8_t* __restrict__ mask,
+                                                                float* __restrict__ pooled,
+                                                                uint32_t* __restrict__ idx) {
+    const int Q = 1 << q_shift, C = 4 * Q;
+    const int j = blockIdx.x * kThreads + threadIdx.x;
+    if (j >= p.Wo * Q) return;
+    const int row = blockIdx.y, b = row / p.Ho, oy = row - b * p.Ho;
+    const int c = 4 * (j & (Q - 1)), ox = j >> q_shift;
+    const int gc = (b / p.ipg) * C + c;
+    const float4 mu = ld4(smean + gc), is = ld4(sinvstd + gc), ga = ld4(gamma + c), be = ld4(beta + c);
+    float m[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    const int k0 = (oy == 0 ? 3 : 0) + (ox == 0 ? 1 : 0);   // first tap inside the image
+    int a[4] = {k0, k0, k0, k0};
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky) {
+        const int iy = 2 * oy - 1 + ky;
+        if (iy < 0 || iy >= p.H) continue;
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx) {
+            const int ix = 2 * ox - 1 + kx;
+            if (ix < 0 || ix >= p.W) continue;
+            const size_t e = (((size_t)b * p.H + iy) * p.W + ix) * C + c;
+            const float4 o = md2::relu4(md2::bn_affine4(ld4(z + e), mu, is, ga, be));
+            const int k = ky * 3 + kx;
+            md2::pool_take(o.x, k, m[0], a[0]);
+            md2::pool_take(o.y, k, m[1], a[1]);
+            md2::pool_take(o.z, k, m[2], a[2]);
+            md2::pool_take(o.w, k, m[3], a[3]);
+            if (ky >= 1 && kx >= 1) {   // this thread's own 2x2 input pixels (inside: H, W even)
+                if (YOUT) st4(y + e, o);
+                mask[e >> 2] = (uint8_t)((stored_pos<float>(o.x) ? 1 : 0) | (stored_pos<float>(o.y) ? 2 : 0) |
+                                         (stored_pos<float>(o.z) ? 4 : 0) | (stored_pos<float>(o.w) ? 8 : 0));
+            }
+        }
+    }
+    const size_t o = (((size_t)b * p.Ho + oy) * p.Wo + ox) * C + c;
+    st4(pooled + o, make_float4(m[0], m[1], m[2], m[3]));
+    idx[o >> 2] = (uint32_t)a[0] | ((uint32_t)a[1] << 8) | ((uint32_t)a[2] << 16) | ((uint32_t)a[3] << 24);
+}
+
+// batch statistics: partial sums, then mean / invstd / running statistics per channel
 template <typename T>
-void launch_fwd(const md2_bn_desc* d, const void* x, const float* gamma, const float* beta, const void* residual,
-                float* running_mean, float* running_var, void* y, float* save_mean, float* save_invstd,
-                void* workspace, hipStream_t st, uint8_t* mask = nullptr) {
+void launch_stats(const md2_bn_desc* d, const void* x, float* running_mean, float* running_var, float* save_mean,
+                  float* save_invstd, void* workspace, hipStream_t st) {
     const int NG = groups_of(d);
     const long long P = d->pixels / NG;   // per group
     const int C = d->channels, G = blocks_for_stats(P, C);
@@ -646,6 +701,16 @@ void launch_fwd(const md2_bn_desc* d, const void* x, const float* gamma, const f
         hipLaunchKernelGGL(bn_stats_kernel<T>, dim3(G, NG), dim3(kThreads), 0, st, x, P, C, G, workspace);
     hipLaunchKernelGGL(bn_stats_final_kernel, dim3(C), dim3(kThreads), 0, st, P, C, G, NG, d->eps, d->momentum,
                        running_mean, running_var, save_mean, save_invstd, workspace);
+}
+
+template <typename T>
+void launch_fwd(const md2_bn_desc* d, const void* x, const float* gamma, const float* beta, const void* residual,
+                float* running_mean, float* running_var, void* y, float* save_mean, float* save_invstd,
+                void* workspace, hipStream_t st, uint8_t* mask = nullptr) {
+    const int NG = groups_of(d);
+    const long long P = d->pixels / NG;   // per group
+    const int C = d->channels;
+    launch_stats<T>(d, x, running_mean, running_var, save_mean, save_invstd, workspace, st);
     const int n4g = (int)(P * C / 4);
     const bool relu = d->flags & MD2_BN_RELU, res = d->flags & MD2_BN_RESIDUAL;
     if (sizeof(T) == 2 && C % 8 == 0 && apply8_on()) {
@@ -663,15 +728,15 @@ void launch_fwd(const md2_bn_desc* d, const void* x, const float* gamma, const f
                        save_invstd, y, n4g, C / 4, mask);
 }
 
+// the backward's reductions: dγ, dβ and the dx coefficient rows left in the workspace
 template <typename T>
-void launch_bwd(const md2_bn_desc* d, const void* x, const void* y, const void* grad_y, const void* grad_y2,
-                const void* grad_y3, const float* gamma,
-                const float* save_mean, const float* save_invstd, void* grad_x, void* grad_residual,
-                float* grad_gamma, float* grad_beta, void* workspace, hipStream_t st, bool mask_in = false) {
+void launch_bwd_reduce(const md2_bn_desc* d, const void* x, const void* y, const void* grad_y, const void* grad_y2,
+                       const void* grad_y3, const float* gamma, const float* save_mean, const float* save_invstd,
+                       float* grad_gamma, float* grad_beta, void* workspace, hipStream_t st, bool mask_in) {
     const int NG = groups_of(d);
     const long long P = d->pixels / NG;
     const int C = d->channels, G = blocks_for_stats(P, C);
-    const bool relu = d->flags & MD2_BN_RELU, res = d->flags & MD2_BN_RESIDUAL;
+    const bool relu = d->flags & MD2_BN_RELU;
     // mask_in: y is the forward's ReLU mask (one byte per element quad), not y itself
     auto red = relu ? (mask_in ? bn_bwd_reduce_kernel<T, true, true> : bn_bwd_reduce_kernel<T, true>)
                     : bn_bwd_reduce_kernel<T, false>;
@@ -682,6 +747,19 @@ void launch_bwd(const md2_bn_desc* d, const void* x, const void* y, const void* 
                        workspace);
     hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(C), dim3(kThreads), 0, st, P, C, G, NG, gamma, save_invstd,
                        grad_gamma, grad_beta, workspace);
+}
+
+template <typename T>
+void launch_bwd(const md2_bn_desc* d, const void* x, const void* y, const void* grad_y, const void* grad_y2,
+                const void* grad_y3, const float* gamma,
+                const float* save_mean, const float* save_invstd, void* grad_x, void* grad_residual,
+                float* grad_gamma, float* grad_beta, void* workspace, hipStream_t st, bool mask_in = false) {
+    const int NG = groups_of(d);
+    const long long P = d->pixels / NG;
+    const int C = d->channels, G = blocks_for_stats(P, C);
+    const bool relu = d->flags & MD2_BN_RELU, res = d->flags & MD2_BN_RESIDUAL;
+    launch_bwd_reduce<T>(d, x, y, grad_y, grad_y2, grad_y3, gamma, save_mean, save_invstd, grad_gamma, grad_beta,
+                         workspace, st, mask_in);
     const int n4g = (int)(P * C / 4);
     const float* coef = work(workspace, G, C, NG).coef;
     if (sizeof(T) == 2 && C % 8 == 0 && apply8_on()) {
@@ -770,6 +848,77 @@ int md2_bn_bwd_mask(const md2_bn_desc* d, const void* x, const uint8_t* relu_mas
     if (!(d && (d->flags & MD2_BN_RELU))) return md2_report_error(MD2_ERR_ARG, "bn_bwd_mask: needs MD2_BN_RELU");
     return bn_bwd_impl(d, x, relu_mask, true, grad_y, grad_y2, grad_y3, gamma, save_mean, save_invstd, grad_x,
                        grad_residual, grad_gamma, grad_beta, workspace, stream);
+}
+
+// the fused stem pass takes fp32, ReLU without a residual, even H and W
+static bool stem_pool_geom(const md2_bn_desc* d, int height, int width, StemPoolGeom& p) {
+    if (!valid(d) || (d->flags & (MD2_BN_RELU | MD2_BN_RESIDUAL | MD2_BN_BF16)) != MD2_BN_RELU) return false;
+    if (height < 2 || width < 2 || (height & 1) || (width & 1)) return false;
+    const long long hw = (long long)height * width;
+    if (d->pixels % hw) return false;
+    const long long B = d->pixels / hw;
+    const int NG = groups_of(d);
+    if (B % NG || B * (height / 2) > 65535) return false;   // blockIdx.y = b·Ho + oy
+    p.B = (int)B;
+    p.H = height;
+    p.W = width;
+    p.Ho = height / 2;
+    p.Wo = width / 2;
+    p.ipg = (int)(B / NG);
+    return true;
+}
+
+int md2_bn_pool_fwd_supported(const md2_bn_desc* d, int height, int width) {
+    StemPoolGeom p;
+    return stem_pool_geom(d, height, width, p) ? 1 : 0;
+}
+
+int md2_bn_pool_fwd(const md2_bn_desc* d, int height, int width, const float* x, const float* gamma,
+                    const float* beta, float* running_mean, float* running_var, float* y, uint8_t* relu_mask,
+                    float* pooled, uint32_t* idx, float* save_mean, float* save_invstd, void* workspace,
+                    void* stream) {
+    StemPoolGeom p;
+    if (!stem_pool_geom(d, height, width, p))
+        return md2_report_error(MD2_ERR_ARG, "bn_pool_fwd: fp32, MD2_BN_RELU alone, even height and width, "
+                                             "batch * height / 2 <= 65535");
+    if (!x || !gamma || !beta || !relu_mask || !pooled || !idx || !save_mean || !save_invstd || !workspace ||
+        (!running_mean != !running_var))
+        return md2_report_error(MD2_ERR_ARG, "bn_pool_fwd: NULL operand");
+    const hipStream_t st = (hipStream_t)stream;
+    launch_stats<float>(d, x, running_mean, running_var, save_mean, save_invstd, workspace, st);
+    const int Q = d->channels / 4;
+    int sh = 0;
+    while ((1 << sh) < Q) ++sh;
+    auto k = y ? bn_relu_pool_kernel<true> : bn_relu_pool_kernel<false>;
+    hipLaunchKernelGGL(k, dim3((p.Wo * Q + kThreads - 1) / kThreads, p.B * p.Ho), dim3(kThreads), 0, st, p, sh, x,
+                       gamma, beta, save_mean, save_invstd, y, relu_mask, pooled, idx);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? MD2_OK : md2_report_error(MD2_ERR_HIP, hipGetErrorString(e));
+}
+
+int md2_bn_bwd_reduce_mask(const md2_bn_desc* d, const void* x, const uint8_t* relu_mask, const void* grad_y,
+                           const float* gamma, const float* save_mean, const float* save_invstd, float* grad_gamma,
+                           float* grad_beta, void* workspace, void* stream) {
+    if (!valid(d)) return md2_report_error(MD2_ERR_ARG, "bn: unsupported shape");
+    if (!(d->flags & MD2_BN_RELU)) return md2_report_error(MD2_ERR_ARG, "bn_bwd_reduce_mask: needs MD2_BN_RELU");
+    if (!x || !relu_mask || !grad_y || !gamma || !save_mean || !save_invstd || !grad_gamma || !grad_beta ||
+        !workspace)
+        return md2_report_error(MD2_ERR_ARG, "bn_bwd_reduce_mask: NULL operand");
+    if (d->flags & MD2_BN_BF16)
+        launch_bwd_reduce<uint16_t>(d, x, relu_mask, grad_y, nullptr, nullptr, gamma, save_mean, save_invstd,
+                                    grad_gamma, grad_beta, workspace, (hipStream_t)stream, true);
+    else
+        launch_bwd_reduce<float>(d, x, relu_mask, grad_y, nullptr, nullptr, gamma, save_mean, save_invstd,
+                                 grad_gamma, grad_beta, workspace, (hipStream_t)stream, true);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? MD2_OK : md2_report_error(MD2_ERR_HIP, hipGetErrorString(e));
+}
+
+size_t md2_bn_coef_offset(const md2_bn_desc* d) {
+    if (!valid(d)) return 0;
+    const int NG = groups_of(d);
+    const int G = blocks_for_stats(d->pixels / NG, d->channels);
+    return 2 * (size_t)NG * G * d->channels * sizeof(float);
 }
 
 int md2_bn_bwd(const md2_bn_desc* d, const void* x, const void* y, const void* grad_y, const float* gamma,

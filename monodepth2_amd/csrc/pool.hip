@@ -16,6 +16,7 @@
 #include <stdlib.h>
 
 #include "md2_bf16.h"
+#include "md2_bn_expr.h"
 #include "md2hot.h"
 
 int md2_report_error(int code, const char* msg);
@@ -28,12 +29,8 @@ struct PoolArgs {
     int B, H, W, C, Ho, Wo;
 };
 
-__device__ __forceinline__ void take(float v, int k, float& m, int& a) {
-    if (v > m || isnan(v)) {   // ATen max_pool2d: strictly greater, or NaN
-        m = v;
-        a = k;
-    }
-}
+// ATen max_pool2d's tap rule (md2_bn_expr.h: shared with the stem's fused BatchNorm + pool)
+__device__ __forceinline__ void take(float v, int k, float& m, int& a) { md2::pool_take(v, k, m, a); }
 
 template <typename T>
 __global__ void __launch_bounds__(kThreads) maxpool_fwd_kernel(PoolArgs p, const void* __restrict__ x,

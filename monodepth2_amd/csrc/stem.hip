@@ -26,6 +26,8 @@
 // ranges (K splits) and write fp32 partials [group][split][64][147]; a second launch
 // sums them in split order into dW in the weight's memory format — deterministic,
 // no atomics.
+// md2_stem_wgrad_bn: dy is the input gradient of the BatchNorm behind the stem, which the
+// transposed-read kernel forms on load (FUSE) instead of reading it from memory.
 // Layouts: x (B,H,W,C) and dy (B,Ho,Wo,64) channels_last fp32; dW channels_last
 // [co][ky][kx][ci] (MD2_STEM_WEIGHT_CL) or contiguous [co][ci][ky][kx].
 
@@ -38,6 +40,7 @@
 #include <algorithm>
 #include <stdlib.h>
 
+#include "md2_bn_expr.h"
 #include "md2hot.h"
 
 int md2_report_error(int code, const char* msg);
@@ -76,6 +79,13 @@ struct StemArgs {
     const float* gy;
     float* part;                        // [group][split][64][147]
     float* gw;
+    // FUSE (md2_stem_wgrad_bn): gy is the gradient of relu(bn(z)); the kernel forms the
+    // stem output's gradient from it on load (BatchNorm backward apply, md2_bn_expr.h)
+    const float* z;                     // the stem output (B,Ho,Wo,64)
+    const uint8_t* mask;                // the forward's ReLU mask, one byte per element quad
+    const float* mean;                  // [bn_groups][64]
+    const float* coef;                  // [3][bn_groups][64]: bn_bwd_final's k1, k2, k3
+    int bn_groups, bn_ipg;              // BatchNorm groups, images per group
 };
 
 // Exact three-way split by truncation (conv.hip): x == x0 + x1 + x2, each a bf16
@@ -366,8 +376,30 @@ __device__ __forceinline__ bf16x8 tr_pair(const __bf16* lo, const __bf16* hi) {
 }
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-template <int C, bool BF = false, bool PF = BF>
+// FUSE: dy is not in memory — the BatchNorm backward's apply pass is folded into the dy
+// fetch: dy = k1·(g' - k2 - (z - mean)·k3) with g' = g gated by the ReLU mask, per channel
+// quad (fixed per thread: kTThreads is a multiple of 16) and BatchNorm group (the chunk's
+// image), in bn_bwd_apply_kernel's expressions; the row's padding pixels stay zero.
+struct BnCoef {
+    float4 mu, k1, k2, k3;
+};
+__device__ __forceinline__ BnCoef bn_coef(const StemArgs& a, int b, int co4) {
+    const int gc = (b / a.bn_ipg) * kCo + 4 * co4, s = a.bn_groups * kCo;
+    BnCoef c;
+    c.mu = *(const float4*)(a.mean + gc);
+    c.k1 = *(const float4*)(a.coef + gc);
+    c.k2 = *(const float4*)(a.coef + s + gc);
+    c.k3 = *(const float4*)(a.coef + 2 * s + gc);
+    return c;
+}
+__device__ __forceinline__ float4 bn_dy(const BnCoef& c, uint32_t m, const float4 g, const float4 z) {
+    return md2::bn_bwd_dx4(md2::relu_gate_bits4(m, g), z, c.mu, c.k1, c.k2, c.k3);
+}
+
+template <int C, bool BF = false, bool PF = BF, bool FUSE = false>
 __global__ __launch_bounds__(kTThreads, 2) void stem_x6_wgrad_tr_kernel(StemArgs a) {
+    static_assert(!(BF && FUSE), "the fused BatchNorm backward is fp32");
+    static_assert(kTThreads % 16 == 0, "one channel quad per thread");
     // CP: channels per staged column — 3 padded to 4 (a column pair is then 8-byte
     // aligned for the tr read); 6 unpadded (24-byte column pairs are 8-byte aligned, a
     // 4-element read may run into the next column, which is the next window tap anyway):
@@ -438,6 +470,10 @@ __global__ __launch_bounds__(kTThreads, 2) void stem_x6_wgrad_tr_kernel(StemArgs
         constexpr int LX = (NXT + kTThreads - 1) / kTThreads;
         using RT = typename std::conditional<BF, uint2, float4>::type;
         RT rg[LG], rx[LX];
+        // FUSE: z and the mask byte travel with g to the store, where dy is formed (the
+        // fetch stays a pure prefetch); bit 8 of the mask word marks a padding pixel
+        float4 rz[FUSE ? LG : 1];
+        uint32_t rm[FUSE ? LG : 1];
         auto put3 = [&](__bf16* base, int stride, int o, float4 v) {   // three exact planes
             const float e[4] = {v.x, v.y, v.z, v.w};
             float c[3][4];
@@ -463,6 +499,11 @@ __global__ __launch_bounds__(kTThreads, 2) void stem_x6_wgrad_tr_kernel(StemArgs
                 const size_t go = ((size_t)(b * a.Ho + oh) * a.Wo + ow) * kCo + 4 * co4;
                 if constexpr (BF) rg[k] = (i < NGT && ow < a.Wo) ? *(const uint2*)(gh + go) : uint2{0u, 0u};
                 else rg[k] = (i < NGT && ow < a.Wo) ? *(const float4*)(a.gy + go) : float4{0.f, 0.f, 0.f, 0.f};
+                if constexpr (FUSE) {
+                    const bool in = i < NGT && ow < a.Wo;
+                    rz[k] = in ? *(const float4*)(a.z + go) : float4{0.f, 0.f, 0.f, 0.f};
+                    rm[k] = in ? (uint32_t)a.mask[go >> 2] : 0x100u;
+                }
             }
             if constexpr (BF) {
 #pragma unroll
@@ -543,11 +584,16 @@ __global__ __launch_bounds__(kTThreads, 2) void stem_x6_wgrad_tr_kernel(StemArgs
         };
         if (n > 0) fetch(t0);
         for (int t = 0; t < n; ++t) {
+            BnCoef bc;
+            if constexpr (FUSE) bc = bn_coef(a, (t0 + t) / (a.nseg * a.Ho), tid & 15);
 #pragma unroll
             for (int k = 0; k < LG; ++k) {
                 const int i = tid + k * kTThreads;
                 if (NGT % kTThreads && i >= NGT) break;
                 if constexpr (BF) *(u32x2*)&gs[0][tr_goff(i >> 4, i & 15)] = u32x2{rg[k].x, rg[k].y};
+                else if constexpr (FUSE)
+                    put3(&gs[0][0], GE, tr_goff(i >> 4, i & 15),
+                         (rm[k] & 0x100u) ? rg[k] : bn_dy(bc, rm[k], rg[k], rz[k]));
                 else put3(&gs[0][0], GE, tr_goff(i >> 4, i & 15), rg[k]);
             }
 #pragma unroll
@@ -581,6 +627,8 @@ __global__ __launch_bounds__(kTThreads, 2) void stem_x6_wgrad_tr_kernel(StemArgs
         const int seg = rem / a.Ho, oh = rem - seg * a.Ho;
         const int ow0 = seg * kTSeg, iw0 = 2 * ow0 - 3;
         // dy: 64 pixels x 16 channel quads
+        BnCoef bc;
+        if constexpr (FUSE) bc = bn_coef(a, b, tid & 15);
         for (int i = tid; i < kTSeg * 16; i += kTThreads) {
             const int px = i >> 4, co4 = i & 15, ow = ow0 + px;
             if constexpr (BF) {
@@ -590,7 +638,11 @@ __global__ __launch_bounds__(kTThreads, 2) void stem_x6_wgrad_tr_kernel(StemArgs
                 continue;
             }
             float4 v = {0.f, 0.f, 0.f, 0.f};
-            if (ow < a.Wo) v = *(const float4*)(a.gy + ((size_t)(b * a.Ho + oh) * a.Wo + ow) * kCo + 4 * co4);
+            if (ow < a.Wo) {
+                const size_t go = ((size_t)(b * a.Ho + oh) * a.Wo + ow) * kCo + 4 * co4;
+                v = *(const float4*)(a.gy + go);
+                if constexpr (FUSE) v = bn_dy(bc, a.mask[go >> 2], v, *(const float4*)(a.z + go));
+            }
             const float e[4] = {v.x, v.y, v.z, v.w};
             float c[3][4];
 #pragma unroll
@@ -1073,8 +1125,9 @@ size_t md2_stem_wgrad_workspace_bytes(const md2_stem_desc* d) {
     return sizeof(float) * (size_t)(a.C / kCG) * a.splits * kCo * kOut;
 }
 
-int md2_stem_wgrad(const md2_stem_desc* d, const float* x, const float* grad_y, float* grad_weight, void* workspace,
-                   void* stream) {
+// fuse: the BatchNorm operands of md2_stem_wgrad_bn (z, mask, mean, coef, bn_groups), or NULL
+static int stem_wgrad_impl(const md2_stem_desc* d, const float* x, const float* grad_y, const StemArgs* fuse,
+                           float* grad_weight, void* workspace, void* stream) {
     if (!valid(d)) return md2_report_error(MD2_ERR_ARG, "stem_wgrad: channels 3/6/9, 32-bit element count");
     if (!x || !grad_y || !grad_weight || !workspace) return md2_report_error(MD2_ERR_ARG, "stem_wgrad: NULL operand");
     const bool tr = use_tr(d);
@@ -1085,19 +1138,37 @@ int md2_stem_wgrad(const md2_stem_desc* d, const float* x, const float* grad_y, 
     a.gy = grad_y;
     a.part = (float*)workspace;
     a.gw = grad_weight;
+    if (fuse) {
+        if (!tr || (d->flags & MD2_STEM_BF16))
+            return md2_report_error(MD2_ERR_ARG, "stem_wgrad_bn: fp32, channels 3 / 6, the transposed-read kernel");
+        if (!fuse->z || !fuse->mask || !fuse->mean || !fuse->coef || fuse->bn_groups < 1 || a.B % fuse->bn_groups)
+            return md2_report_error(MD2_ERR_ARG, "stem_wgrad_bn: NULL operand or batch not a multiple of groups");
+        a.z = fuse->z;
+        a.mask = fuse->mask;
+        a.mean = fuse->mean;
+        a.coef = fuse->coef;
+        a.bn_groups = fuse->bn_groups;
+        a.bn_ipg = a.B / fuse->bn_groups;
+    }
     const int NG = a.C / kCG;
     const hipStream_t st = (hipStream_t)stream;
     if (tr) {
         const bool bf = (d->flags & MD2_STEM_BF16) != 0;
-        static const bool pf32 = [] {   // A/B knob: MD2_STEM_PF32=1 prefetches in the fp32 form too
+        static const bool pf32_env = [] {   // A/B knob: MD2_STEM_PF32=1 prefetches in the fp32 form too
             const char* e = getenv("MD2_STEM_PF32");
             return e && e[0] == '1';
         }();
+        const bool pf32 = pf32_env || (d->flags & MD2_STEM_PREFETCH);
         void (*k)(StemArgs) =
             a.C == 3 ? (bf ? stem_x6_wgrad_tr_kernel<3, true>
                            : (pf32 ? stem_x6_wgrad_tr_kernel<3, false, true> : stem_x6_wgrad_tr_kernel<3>))
                      : (bf ? stem_x6_wgrad_tr_kernel<6, true>
                            : (pf32 ? stem_x6_wgrad_tr_kernel<6, false, true> : stem_x6_wgrad_tr_kernel<6>));
+        if (fuse)
+            k = a.C == 3 ? (pf32 ? stem_x6_wgrad_tr_kernel<3, false, true, true>
+                                 : stem_x6_wgrad_tr_kernel<3, false, false, true>)
+                         : (pf32 ? stem_x6_wgrad_tr_kernel<6, false, true, true>
+                                 : stem_x6_wgrad_tr_kernel<6, false, false, true>);
         hipLaunchKernelGGL(k, dim3(a.splits), dim3(kTThreads), 0, st, a);
     } else {
         void (*k)(StemArgs) =
@@ -1108,6 +1179,27 @@ int md2_stem_wgrad(const md2_stem_desc* d, const float* x, const float* grad_y, 
     hipLaunchKernelGGL(stem_wgrad_final_kernel, dim3((outs + kFinOut - 1) / kFinOut), dim3(256), 0, st, a);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? MD2_OK : md2_report_error(MD2_ERR_HIP, hipGetErrorString(e));
+}
+
+int md2_stem_wgrad(const md2_stem_desc* d, const float* x, const float* grad_y, float* grad_weight, void* workspace,
+                   void* stream) {
+    return stem_wgrad_impl(d, x, grad_y, nullptr, grad_weight, workspace, stream);
+}
+
+int md2_stem_wgrad_bn_supported(const md2_stem_desc* d) {
+    return valid(d) && use_tr(d) && !(d->flags & MD2_STEM_BF16);
+}
+
+int md2_stem_wgrad_bn(const md2_stem_desc* d, const float* x, const float* grad, const float* z,
+                      const uint8_t* relu_mask, const float* save_mean, const float* coef, int bn_groups,
+                      float* grad_weight, void* workspace, void* stream) {
+    StemArgs f = {};
+    f.z = z;
+    f.mask = relu_mask;
+    f.mean = save_mean;
+    f.coef = coef;
+    f.bn_groups = bn_groups;
+    return stem_wgrad_impl(d, x, grad, &f, grad_weight, workspace, stream);
 }
 
 int md2_stem_fwd(const md2_stem_desc* d, const float* x, const float* weight, float* y, void* stream) {

@@ -19,9 +19,9 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from ..bn_ops import bn_act, max_pool_3x3s2, max_pool_3x3s2_with_alias
+from ..bn_ops import bn_act
 from ..conv_ops import conv2d
-from ..stem_ops import stem_conv
+from ..stem_ops import stem_bn_pool
 
 
 def _conv3x3(cin, cout, stride=1):
@@ -192,13 +192,16 @@ class ResnetEncoder(nn.Module):
     def forward(self, input_image):
         return self.forward_prepared(self.prepare(input_image))
 
-    def forward_prepared(self, x):
-        """The encoder on an input already normalised by `prepare`."""
+    def forward_prepared(self, x, need_f0: bool = True):
+        """The encoder on an input already normalised by `prepare`.  need_f0=False (a
+        caller that reads the last feature only, as the PoseDecoder does): features[0] is
+        None and the fused stem never materialises it."""
         e = self.encoder
-        f0 = bn_act(e.bn1, stem_conv(e.conv1, x))   # weight gradient on f32 MFMA (stem_ops)
+        # conv1 -> bn1 -> relu -> maxpool as one node (stem_ops.stem_bn_pool: weight gradient
+        # on f32 MFMA, the BatchNorm elementwise passes folded into the pool and into it).
         # f0's two gradients (layer1, decoder skip) and the pooled map's two (the first
         # block's conv1 and shortcut) all meet in the pool backward
-        x, xs, f0 = max_pool_3x3s2_with_alias(e.maxpool, f0, out_alias=True)
+        x, xs, f0 = stem_bn_pool(e.conv1, e.bn1, e.maxpool, x, need_f0=need_f0)
         feats = [f0]
         layers = [e.layer1, e.layer2, e.layer3, e.layer4]
         for li, layer in enumerate(layers):

@@ -364,7 +364,7 @@ class Trainer:
                 enc = models["pose_encoder"]
                 x = enc.prepare(pairs)
                 with bn_groups(len(temporal)):
-                    feats = enc.forward_prepared(x)
+                    feats = enc.forward_prepared(x, need_f0=False)   # the PoseDecoder reads feats[-1] alone
                 dec = getattr(models["pose"], "module", models["pose"])   # DDP-wrapped or not
                 dec.packed_output = True
                 try:
