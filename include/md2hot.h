@@ -436,6 +436,33 @@ int md2_aug_run2(md2_aug_plan* plan, const uint8_t* frames, const md2_aug_item* 
                  float* const* color, float* const* color_aug, uint32_t* src8, void* stream);
 
 /*
+ * Mixed decoded sizes in one batch (ABI 24, new symbols): KITTI raw has four frame
+ * sizes by recording date and a shuffled batch mixes them (each item is resized on its
+ * own, mono_dataset.py:96-101).  sizes: num_sizes (1..16) pairs (in_height, in_width),
+ * the plan's size classes; desc->in_height / in_width are ignored.  One set of scale-0
+ * LANCZOS tables per class (host, double, as PIL); levels 1.. are built once; scratch
+ * is sized for the largest class.  A mixed plan runs through md2_aug_run_mixed only.
+ */
+md2_aug_plan* md2_aug_plan_create_mixed(const md2_aug_desc* desc, const int32_t* sizes, int num_sizes);
+/*
+ * frames_base: ONE device uint8 buffer of total_bytes holding frame f of item b as a
+ * tight (h_c, w_c, 3) image at byte frame_offset[f*B + b] (its allocation must reach
+ * total_bytes rounded up to 4: rows are fetched as aligned dwords);
+ * frame_offset: HOST uint64[F*B], every entry a multiple of 16; item_class: HOST
+ * int32[B] indexing `sizes` (all frames of an item share a class: one drive).  Both
+ * travel with `items` through the plan's pinned ring in one upload: no synchronisation
+ * and no allocation per call.  Outputs are md2_aug_run2's, and for every item bit-equal
+ * to a single-size plan run on that item alone (the contrast mean is per image).
+ * Scale 0 is one launch per class present (two-pass classes: h, v and their contrast
+ * sums).  MD2_ERR_ARG, before any launch: a NULL argument, a class out of range, a
+ * misaligned offset, offset + h_c*w_c*3 > total_bytes, a non-permutation order.
+ * Overlapping frames are not refused: frames are only read.
+ */
+int md2_aug_run_mixed(md2_aug_plan* plan, const uint8_t* frames_base, uint64_t total_bytes,
+                      const int32_t* item_class, const uint64_t* frame_offset, const md2_aug_item* items,
+                      float* const* color, float* const* color_aug, uint32_t* src8, void* stream);
+
+/*
  * Training-mode BatchNorm2d (+ residual add) (+ ReLU) on channels_last activations:
  * relu(bn(x)) and relu(bn(x) + identity) of the ResNet encoders' blocks
  * (torchvision BasicBlock / Bottleneck behind networks/resnet_encoder.py:62-98).

@@ -75,7 +75,8 @@ EXPORTS = ["md2_abi_version", "md2_last_error", "md2_workspace_bytes", "md2_sele
            "md2_pose_ate", "md2_pose_ate_workspace_bytes",
            "md2_disp_colorize", "md2_disp_colorize_workspace_bytes",
            "md2_bn_pool_fwd_supported", "md2_bn_pool_fwd", "md2_bn_bwd_reduce_mask", "md2_bn_coef_offset",
-           "md2_stem_wgrad_bn_supported", "md2_stem_wgrad_bn"]
+           "md2_stem_wgrad_bn_supported", "md2_stem_wgrad_bn",
+           "md2_aug_plan_create_mixed", "md2_aug_run_mixed"]
 
 DTYPE_F32 = 0    # md2_desc.disp_dtype
 DTYPE_BF16 = 1
@@ -341,6 +342,12 @@ def _declare(L):
     L.md2_aug_run.argtypes = [_vp, _vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp]
     L.md2_aug_run2.restype = ctypes.c_int
     L.md2_aug_run2.argtypes = [_vp, _vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp]
+    L.md2_aug_plan_create_mixed.restype = _vp
+    L.md2_aug_plan_create_mixed.argtypes = [ctypes.POINTER(AugDesc), ctypes.POINTER(ctypes.c_int32), ctypes.c_int]
+    L.md2_aug_run_mixed.restype = ctypes.c_int
+    L.md2_aug_run_mixed.argtypes = [_vp, _vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_int32),
+                                    ctypes.POINTER(ctypes.c_uint64), _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                    _vp, _vp]
     L.md2_bn_workspace_bytes.restype = ctypes.c_size_t
     L.md2_bn_workspace_bytes.argtypes = [ctypes.POINTER(BnDesc)]
     L.md2_bn_fwd.restype = ctypes.c_int

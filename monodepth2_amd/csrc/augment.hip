@@ -21,6 +21,11 @@
 // Launches per batch: a memset, one fused (h+v, LDS-tiled, contrast-mean summing)
 // resize per pyramid level, then one jitter/to_tensor pass over all levels.
 // Integer atomics only (the contrast sums), so results are deterministic.
+//
+// A batch may mix decoded frame sizes (KITTI raw has four): md2_aug_run_mixed reads the
+// frames from one ragged buffer and runs scale 0 as one launch per size class present,
+// over that class's image list, with that class's tables (the MIXED instances of the
+// resize kernels); the levels above and the jitter pass do not see the input size.
 
 #include <hip/hip_runtime.h>
 
@@ -54,22 +59,34 @@ __device__ __forceinline__ uint8_t clip8(int v) {
     return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
 }
 
+// One size class of a mixed-size batch (md2_aug_run_mixed): the launch covers the
+// images list[0..count) (indices f*B + b), image n starting at byte offs[n] of the
+// ragged frame buffer.  Unused (null) by the single-size entry points.
+struct ClassList {
+    const unsigned long long* offs;
+    const int* list;
+};
+
 // Horizontal LANCZOS pass: (N, h, sw, 3) -> (N, h, dw, 3).  flip_items != nullptr
-// (level 0 only): item b = n % B reads its source columns mirrored.
+// (level 0 only): item b = n % B reads its source columns mirrored.  MIXED: the N
+// images of one size class, gathered from the ragged buffer into a dense (N, ...) dst.
+template <bool MIXED>
 __global__ void __launch_bounds__(kThreads) resize_h_kernel(const uint8_t* __restrict__ src,
                                                             uint8_t* __restrict__ dst, int N, int h, int sw,
                                                             int dw, const int2* __restrict__ bounds,
                                                             const int* __restrict__ kk, int ksize,
-                                                            const md2_aug_item* __restrict__ items, int B) {
+                                                            const md2_aug_item* __restrict__ items, int B,
+                                                            ClassList cl) {
     const size_t total = (size_t)N * h * dw;
     const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
     if (i >= total) return;
     const int x = (int)(i % dw);
     const size_t row = i / dw;   // n*h + y
-    const bool flip = items && items[(int)((row / h) % B)].flip;
+    const int n = MIXED ? cl.list[row / h] : (int)(row / h);
+    const bool flip = items && items[n % B].flip;
     const int2 bd = bounds[x];
     const int* k = kk + (size_t)x * ksize;
-    const uint8_t* s = src + row * sw * 3;
+    const uint8_t* s = MIXED ? src + cl.offs[n] + (row % h) * sw * 3 : src + row * sw * 3;
     int a0 = 1 << (kPrecisionBits - 1), a1 = a0, a2 = a0;
     for (int t = 0; t < bd.y; ++t) {
         const int c = flip ? sw - 1 - (bd.x + t) : bd.x + t;
@@ -84,22 +101,26 @@ __global__ void __launch_bounds__(kThreads) resize_h_kernel(const uint8_t* __res
     o[2] = clip8(a2);
 }
 
-// Vertical LANCZOS pass: (N, sh, w, 3) -> (N, dh, w, 3).
+// Vertical LANCZOS pass: (N, sh, w, 3) -> (N, dh, w, 3).  MIXED: dense image j of the
+// class's intermediate lands at image list[j] of dst / color / rgbx.
+template <bool MIXED>
 __global__ void __launch_bounds__(kThreads) resize_v_kernel(const uint8_t* __restrict__ src,
                                                             uint8_t* __restrict__ dst, int N, int sh, int dh,
                                                             int w, const int2* __restrict__ bounds,
                                                             const int* __restrict__ kk, int ksize,
                                                             float* __restrict__ color, uint32_t* __restrict__ rgbx,
-                                                            int B) {
+                                                            int B, ClassList cl) {
     const size_t total = (size_t)N * dh * w;
-    const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
+    size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
     if (i >= total) return;
     const int x = (int)(i % w);
     const int y = (int)((i / w) % dh);
-    const size_t n = i / ((size_t)w * dh);
+    const size_t j = i / ((size_t)w * dh);
+    const size_t n = MIXED ? (size_t)cl.list[j] : j;
     const int2 bd = bounds[y];
     const int* k = kk + (size_t)y * ksize;
-    const uint8_t* s = src + ((n * sh + bd.x) * w + x) * 3;
+    const uint8_t* s = src + ((j * sh + bd.x) * w + x) * 3;
+    if (MIXED) i += (n - j) * (size_t)w * dh;   // the output pixel's index in the full batch
     const size_t stride = (size_t)w * 3;
     int a0 = 1 << (kPrecisionBits - 1), a1 = a0, a2 = a0;
     for (int t = 0; t < bd.y; ++t) {
@@ -162,16 +183,18 @@ __device__ __forceinline__ void window_taps(const uint32_t (&e)[ND - 1], const i
     }
 }
 
-template <int KX, int KY>
+template <int KX, int KY, bool MIXED>
 __global__ void __launch_bounds__(kThreads) resize_fused_kernel(
     const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, float* __restrict__ color, int sh, int sw, int dh,
     int dw, const int2* __restrict__ bx, const int* __restrict__ kx, const int2* __restrict__ by,
     const int* __restrict__ ky, FusedLds L, const md2_aug_item* __restrict__ items, int B, int flip_level,
-    unsigned long long* __restrict__ sums, uint32_t* __restrict__ rgbx) {
+    unsigned long long* __restrict__ sums, uint32_t* __restrict__ rgbx, ClassList cl) {
     extern __shared__ __align__(16) uint8_t lds[];
     uint8_t* patch = lds + L.patch;
     uint32_t* inter = (uint32_t*)(lds + L.inter);
-    const int n = blockIdx.z;
+    const int n = MIXED ? cl.list[blockIdx.z] : (int)blockIdx.z;
+    // image n of the batch: dense (single-size) or at its offset in the ragged buffer
+    const uint8_t* img = MIXED ? src + cl.offs[n] : src + (size_t)n * sh * sw * 3;
     const int x0 = blockIdx.x * kTileW, y0 = blockIdx.y * kTileH;
     const int tw = min(kTileW, dw - x0), th = min(kTileH, dh - y0);
     const int c0 = bx[x0].x, c1 = bx[x0 + tw - 1].x + bx[x0 + tw - 1].y;
@@ -184,7 +207,7 @@ __global__ void __launch_bounds__(kThreads) resize_fused_kernel(
     const int pc0 = flip ? sw - c1 : c0;   // first source column of the staged segment
     // stage: row r's segment [pc0, pc0 + (c1-c0)) from its 4-byte-aligned start
     for (int r = wave; r < rin; r += kThreads / 64) {
-        const uint8_t* g = src + (((size_t)n * sh + r0 + r) * sw + pc0) * 3;
+        const uint8_t* g = img + ((size_t)(r0 + r) * sw + pc0) * 3;
         const uint32_t* ga = (const uint32_t*)((uintptr_t)g & ~(uintptr_t)3);
         const int nd = ((int)((uintptr_t)g & 3) + cin3 + 3) >> 2;
         for (int j0 = 0; j0 < nd; j0 += 64)
@@ -205,7 +228,7 @@ __global__ void __launch_bounds__(kThreads) resize_fused_kernel(
         // first staged pixel of the window: tap t sits at pixel (first + t), or (first + KX-1-t) flipped
         const int first = flip ? (c1 - 1 - b.x) - (KX - 1) : (b.x - c0);
         for (int r = wave; r < rin; r += kThreads / 64) {
-            const int shift = (int)((uintptr_t)(src + (((size_t)n * sh + r0 + r) * sw + pc0) * 3) & 3);
+            const int shift = (int)((uintptr_t)(img + ((size_t)(r0 + r) * sw + pc0) * 3) & 3);
             const int byte0 = r * L.pitch + shift + first * 3;   // may be < 0 (pad) when clipped
             const uint32_t* q = (const uint32_t*)(patch + (byte0 & ~3));
             const int off = byte0 & 3;
@@ -392,9 +415,11 @@ __device__ __forceinline__ int level_of(const Levels& L, int bx) {
 
 // Contrast degenerate: sum of L over the image as it stands when contrast runs
 // (ImageEnhance.Contrast, ImageStat mean).  Exact integer sums per (level, image).
+// list != nullptr: blockIdx.y walks the images of one size class (md2_aug_run_mixed).
 __global__ void __launch_bounds__(kThreads) mean_kernel(Levels L, int B, const md2_aug_item* __restrict__ items,
-                                                        unsigned long long* __restrict__ sums) {
-    const int n = blockIdx.y;
+                                                        unsigned long long* __restrict__ sums,
+                                                        const int* __restrict__ list) {
+    const int n = list ? list[blockIdx.y] : (int)blockIdx.y;
     const md2_aug_item it = items[n % B];
     if (!it.color_aug) return;
     const int s = level_of(L, blockIdx.x);
@@ -494,28 +519,31 @@ size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 // 7 up-scaling, 9/11/13 down to 2x), nullptr for wider windows (two-pass kernels).
 using FusedFn = void (*)(const uint8_t*, uint8_t*, float*, int, int, int, int, const int2*, const int*,
                          const int2*, const int*, FusedLds, const md2_aug_item*, int, int, unsigned long long*,
-                         uint32_t*);
+                         uint32_t*, ClassList);
 
-template <int KX>
+template <int KX, bool MIXED>
 FusedFn fused_for_ky(int ky) {
     switch (ky) {
-        case 7: return resize_fused_kernel<KX, 7>;
-        case 9: return resize_fused_kernel<KX, 9>;
-        case 11: return resize_fused_kernel<KX, 11>;
-        case 13: return resize_fused_kernel<KX, 13>;
+        case 7: return resize_fused_kernel<KX, 7, MIXED>;
+        case 9: return resize_fused_kernel<KX, 9, MIXED>;
+        case 11: return resize_fused_kernel<KX, 11, MIXED>;
+        case 13: return resize_fused_kernel<KX, 13, MIXED>;
         default: return nullptr;
     }
 }
 
-FusedFn fused_kernel(int kx, int ky) {
+template <bool MIXED>
+FusedFn fused_kernel_for(int kx, int ky) {
     switch (kx) {
-        case 7: return fused_for_ky<7>(ky);
-        case 9: return fused_for_ky<9>(ky);
-        case 11: return fused_for_ky<11>(ky);
-        case 13: return fused_for_ky<13>(ky);
+        case 7: return fused_for_ky<7, MIXED>(ky);
+        case 9: return fused_for_ky<9, MIXED>(ky);
+        case 11: return fused_for_ky<11, MIXED>(ky);
+        case 13: return fused_for_ky<13, MIXED>(ky);
         default: return nullptr;
     }
 }
+
+FusedFn fused_kernel(int kx, int ky) { return fused_kernel_for<false>(kx, ky); }
 
 // LDS layout of resize_fused_kernel for one level: the widest input patch over all
 // tiles.  bytes > 64 KB (extreme down-scaling) selects the two-pass kernels instead.
@@ -539,13 +567,30 @@ FusedLds fused_layout(const std::vector<int2>& bx, const std::vector<int2>& by) 
 
 unsigned blocks_for(size_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 
+constexpr int kMaxClasses = 16;   // decoded frame sizes per mixed-size plan
+
+// The scale-0 resize of one decoded frame size (a single-size plan has one).
+struct SizeClass {
+    int ih, iw;   // decoded size
+    int kx, ky;   // ksize per pass
+    int2* bx;
+    int2* by;
+    int* wx;
+    int* wy;
+    FusedLds lds;
+    bool fused;
+};
+
 }  // namespace
 
 struct md2_aug_plan {
     md2_aug_desc d;
     int N = 0;
+    bool mixed = false;   // built by md2_aug_plan_create_mixed (md2_aug_run_mixed only)
+    int ncls = 0;
+    SizeClass cls[kMaxClasses];                   // scale 0, per decoded size
     int h[MD2_MAX_SCALES], w[MD2_MAX_SCALES];     // level sizes
-    int sh[MD2_MAX_SCALES], sw[MD2_MAX_SCALES];   // their sources
+    int sh[MD2_MAX_SCALES], sw[MD2_MAX_SCALES];   // their sources (scale 0: class 0's)
     int kx[MD2_MAX_SCALES], ky[MD2_MAX_SCALES];   // ksize per pass
     int2* bx[MD2_MAX_SCALES];
     int2* by[MD2_MAX_SCALES];
@@ -556,77 +601,105 @@ struct md2_aug_plan {
     bool fused[MD2_MAX_SCALES];
     uint8_t* mid = nullptr;   // two-pass intermediate (levels that are not fused)
     unsigned long long* sums = nullptr;
-    md2_aug_item* dev_items = nullptr;    // kRing slots of d.items on the device
-    md2_aug_item* host_items = nullptr;   // pinned staging, same shape
+    // kRing staging slots of slot_bytes each, on the device and pinned on the host:
+    // md2_aug_item[B], then for a mixed plan uint64 offs[N] and int32 list[N]
+    char* dev_stage = nullptr;
+    char* host_stage = nullptr;
+    size_t slot_bytes = 0, o_offs = 0, o_list = 0;
     hipEvent_t staged[kRing] = {};        // slot reusable once its upload has run
     int slot = 0;
     void* block = nullptr;
 };
 
-extern "C" {
+namespace {
 
-md2_aug_plan* md2_aug_plan_create(const md2_aug_desc* d) {
-    if (!d) return md2_report_error(MD2_ERR_ARG, "aug desc is NULL"), nullptr;
+md2_aug_plan* plan_build(const md2_aug_desc* d, const int32_t* sizes, int num_sizes, bool mixed) {
     if (d->items < 1 || d->frames < 1 || d->frames > 8)
         return md2_report_error(MD2_ERR_ARG, "aug: need items >= 1 and frames in 1..8"), nullptr;
     if (d->num_scales < 1 || d->num_scales > MD2_MAX_SCALES)
         return md2_report_error(MD2_ERR_ARG, "aug: num_scales must be 1..4"), nullptr;
-    if (d->in_height < 1 || d->in_width < 1 || (d->height >> (d->num_scales - 1)) < 1 ||
-        (d->width >> (d->num_scales - 1)) < 1)
+    bool sizes_ok = true;
+    for (int c = 0; c < num_sizes; ++c) sizes_ok &= sizes[2 * c] >= 1 && sizes[2 * c + 1] >= 1;
+    if (!sizes_ok || (d->height >> (d->num_scales - 1)) < 1 || (d->width >> (d->num_scales - 1)) < 1)
         return md2_report_error(MD2_ERR_ARG, "aug: every pyramid level must be at least 1x1"), nullptr;
     auto* P = new (std::nothrow) md2_aug_plan();
     if (!P) return md2_report_error(MD2_ERR_ARG, "aug: out of host memory"), nullptr;
     P->d = *d;
+    P->d.in_height = sizes[0];
+    P->d.in_width = sizes[1];
     P->N = d->items * d->frames;
-    std::vector<int2> bxh[MD2_MAX_SCALES], byh[MD2_MAX_SCALES];
-    std::vector<int> wxh[MD2_MAX_SCALES], wyh[MD2_MAX_SCALES];
+    P->mixed = mixed;
+    P->ncls = num_sizes;
+    // one table set per (level >= 1) and per size class (level 0); slot t of the lists below
+    const int ntab = num_sizes + d->num_scales - 1;
+    std::vector<std::vector<int2>> bxh(ntab), byh(ntab);
+    std::vector<std::vector<int>> wxh(ntab), wyh(ntab);
+    std::vector<size_t> o_bx(ntab), o_by(ntab), o_wx(ntab), o_wy(ntab);
     size_t off = 0, mid = 0;
-    size_t o_bx[MD2_MAX_SCALES], o_by[MD2_MAX_SCALES], o_wx[MD2_MAX_SCALES], o_wy[MD2_MAX_SCALES],
-        o_pyr[MD2_MAX_SCALES];
+    size_t o_pyr[MD2_MAX_SCALES];
     for (int s = 0; s < d->num_scales; ++s) {
         P->h[s] = d->height >> s;
         P->w[s] = d->width >> s;
-        P->sh[s] = s ? P->h[s - 1] : d->in_height;
-        P->sw[s] = s ? P->w[s - 1] : d->in_width;
-        P->kx[s] = lanczos_ksize(P->sw[s], P->w[s]);
-        P->ky[s] = lanczos_ksize(P->sh[s], P->h[s]);
-        lanczos_tables(P->sw[s], P->w[s], bxh[s], wxh[s]);
-        lanczos_tables(P->sh[s], P->h[s], byh[s], wyh[s]);
-        o_bx[s] = off; off = align256(off + bxh[s].size() * sizeof(int2));
-        o_by[s] = off; off = align256(off + byh[s].size() * sizeof(int2));
-        o_wx[s] = off; off = align256(off + wxh[s].size() * sizeof(int));
-        o_wy[s] = off; off = align256(off + wyh[s].size() * sizeof(int));
         o_pyr[s] = off; off = align256(off + (size_t)P->N * P->h[s] * P->w[s] * 3);
-        P->lds[s] = fused_layout(bxh[s], byh[s]);
-        P->fused[s] = P->lds[s].bytes <= 64 * 1024 && fused_kernel(P->kx[s], P->ky[s]) != nullptr;
-        const size_t m = (size_t)P->N * P->sh[s] * P->w[s] * 3;
-        if (!P->fused[s] && m > mid) mid = m;
+    }
+    for (int t = 0; t < ntab; ++t) {
+        const bool level0 = t < num_sizes;
+        const int s = level0 ? 0 : t - num_sizes + 1;
+        const int sh = level0 ? sizes[2 * t] : P->h[s - 1], sw = level0 ? sizes[2 * t + 1] : P->w[s - 1];
+        lanczos_tables(sw, P->w[s], bxh[t], wxh[t]);
+        lanczos_tables(sh, P->h[s], byh[t], wyh[t]);
+        o_bx[t] = off; off = align256(off + bxh[t].size() * sizeof(int2));
+        o_by[t] = off; off = align256(off + byh[t].size() * sizeof(int2));
+        o_wx[t] = off; off = align256(off + wxh[t].size() * sizeof(int));
+        o_wy[t] = off; off = align256(off + wyh[t].size() * sizeof(int));
+        const int kx = lanczos_ksize(sw, P->w[s]), ky = lanczos_ksize(sh, P->h[s]);
+        const FusedLds lds = fused_layout(bxh[t], byh[t]);
+        const bool fused = lds.bytes <= 64 * 1024 && fused_kernel(kx, ky) != nullptr;
+        const size_t m = (size_t)P->N * sh * P->w[s] * 3;   // scratch for the largest class
+        if (!fused && m > mid) mid = m;
+        if (level0) {
+            SizeClass& C = P->cls[t];
+            C.ih = sh; C.iw = sw; C.kx = kx; C.ky = ky; C.lds = lds; C.fused = fused;
+        }
+        if (!level0 || t == 0) {
+            P->sh[s] = sh; P->sw[s] = sw; P->kx[s] = kx; P->ky[s] = ky; P->lds[s] = lds; P->fused[s] = fused;
+        }
     }
     const size_t o_mid = off;
     off = align256(off + mid);
     const size_t o_sums = off;
     off = align256(off + (size_t)P->N * d->num_scales * sizeof(unsigned long long));
-    const size_t o_items = off;
-    const size_t item_bytes = (size_t)kRing * d->items * sizeof(md2_aug_item);
-    off = align256(off + item_bytes);
+    const size_t o_stage = off;
+    P->slot_bytes = (size_t)d->items * sizeof(md2_aug_item);   // 20 bytes an item: a multiple of 4 only
+    if (mixed) {
+        P->o_offs = (P->slot_bytes + 15) / 16 * 16;   // the 64-bit offsets start aligned whatever the batch size
+        P->o_list = P->o_offs + (size_t)P->N * sizeof(unsigned long long);
+        P->slot_bytes = align256(P->o_list + (size_t)P->N * sizeof(int));
+    }
+    off = align256(off + kRing * P->slot_bytes);
     if (hipMalloc(&P->block, off) != hipSuccess) {
         delete P;
         return md2_report_error(MD2_ERR_HIP, "aug: hipMalloc of the pyramid scratch failed"), nullptr;
     }
     char* base = (char*)P->block;
-    for (int s = 0; s < d->num_scales; ++s) {
-        P->bx[s] = (int2*)(base + o_bx[s]);
-        P->by[s] = (int2*)(base + o_by[s]);
-        P->wx[s] = (int*)(base + o_wx[s]);
-        P->wy[s] = (int*)(base + o_wy[s]);
-        P->pyr[s] = (uint8_t*)(base + o_pyr[s]);
-        hipError_t e = hipMemcpy(P->bx[s], bxh[s].data(), bxh[s].size() * sizeof(int2), hipMemcpyHostToDevice);
-        if (e == hipSuccess)
-            e = hipMemcpy(P->by[s], byh[s].data(), byh[s].size() * sizeof(int2), hipMemcpyHostToDevice);
-        if (e == hipSuccess)
-            e = hipMemcpy(P->wx[s], wxh[s].data(), wxh[s].size() * sizeof(int), hipMemcpyHostToDevice);
-        if (e == hipSuccess)
-            e = hipMemcpy(P->wy[s], wyh[s].data(), wyh[s].size() * sizeof(int), hipMemcpyHostToDevice);
+    for (int s = 0; s < d->num_scales; ++s) P->pyr[s] = (uint8_t*)(base + o_pyr[s]);
+    for (int t = 0; t < ntab; ++t) {
+        int2* bx = (int2*)(base + o_bx[t]);
+        int2* by = (int2*)(base + o_by[t]);
+        int* wx = (int*)(base + o_wx[t]);
+        int* wy = (int*)(base + o_wy[t]);
+        if (t < num_sizes) {
+            SizeClass& C = P->cls[t];
+            C.bx = bx; C.by = by; C.wx = wx; C.wy = wy;
+        }
+        if (t >= num_sizes || t == 0) {
+            const int s = t < num_sizes ? 0 : t - num_sizes + 1;
+            P->bx[s] = bx; P->by[s] = by; P->wx[s] = wx; P->wy[s] = wy;
+        }
+        hipError_t e = hipMemcpy(bx, bxh[t].data(), bxh[t].size() * sizeof(int2), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(by, byh[t].data(), byh[t].size() * sizeof(int2), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(wx, wxh[t].data(), wxh[t].size() * sizeof(int), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(wy, wyh[t].data(), wyh[t].size() * sizeof(int), hipMemcpyHostToDevice);
         if (e != hipSuccess) {
             (void)hipFree(P->block);
             delete P;
@@ -635,8 +708,8 @@ md2_aug_plan* md2_aug_plan_create(const md2_aug_desc* d) {
     }
     P->mid = (uint8_t*)(base + o_mid);
     P->sums = (unsigned long long*)(base + o_sums);
-    P->dev_items = (md2_aug_item*)(base + o_items);
-    bool ok = hipHostMalloc((void**)&P->host_items, item_bytes, hipHostMallocDefault) == hipSuccess;
+    P->dev_stage = base + o_stage;
+    bool ok = hipHostMalloc((void**)&P->host_stage, kRing * P->slot_bytes, hipHostMallocDefault) == hipSuccess;
     for (int r = 0; ok && r < kRing; ++r)
         ok = hipEventCreateWithFlags(&P->staged[r], hipEventDisableTiming) == hipSuccess;
     if (!ok) {
@@ -646,6 +719,80 @@ md2_aug_plan* md2_aug_plan_create(const md2_aug_desc* d) {
     return P;
 }
 
+bool orders_ok(const md2_aug_item* host_items, int B) {
+    for (int b = 0; b < B; ++b) {
+        unsigned seen = 0;
+        for (int k = 0; k < 4; ++k) seen |= host_items[b].order[k] < 4 ? 1u << host_items[b].order[k] : 16u;
+        if (seen != 15u) return false;
+    }
+    return true;
+}
+
+// Pyramid level s >= 1 (or scale 0 of a single-size plan) for the whole batch.
+void launch_level(md2_aug_plan* P, int s, const uint8_t* src, const md2_aug_item* items, float* color,
+                  uint32_t* src8, hipStream_t st) {
+    const int N = P->N, B = P->d.items;
+    if (P->fused[s]) {
+        const dim3 grid((P->w[s] + kTileW - 1) / kTileW, (P->h[s] + kTileH - 1) / kTileH, N);
+        hipLaunchKernelGGL(fused_kernel(P->kx[s], P->ky[s]), grid, dim3(kThreads), P->lds[s].bytes, st, src,
+                           P->pyr[s], color, P->sh[s], P->sw[s], P->h[s], P->w[s], P->bx[s], P->wx[s], P->by[s],
+                           P->wy[s], P->lds[s], items, B, s == 0 ? 1 : 0, P->sums + (size_t)s * N,
+                           s == 0 ? src8 : nullptr, ClassList{});
+    } else {
+        hipLaunchKernelGGL(resize_h_kernel<false>, dim3(blocks_for((size_t)N * P->sh[s] * P->w[s])),
+                           dim3(kThreads), 0, st, src, P->mid, N, P->sh[s], P->sw[s], P->w[s], P->bx[s], P->wx[s],
+                           P->kx[s], s ? nullptr : items, B, ClassList{});
+        hipLaunchKernelGGL(resize_v_kernel<false>, dim3(blocks_for((size_t)N * P->h[s] * P->w[s])),
+                           dim3(kThreads), 0, st, P->mid, P->pyr[s], N, P->sh[s], P->h[s], P->w[s], P->by[s],
+                           P->wy[s], P->ky[s], color, s == 0 ? src8 : nullptr, B, ClassList{});
+    }
+}
+
+// The contrast means of the two-pass levels from `first_level` on, then the jitter /
+// to_tensor pass over every level.
+void launch_jitter(md2_aug_plan* P, int first_level, const md2_aug_item* items, float* const* color_aug,
+                   hipStream_t st) {
+    const md2_aug_desc& d = P->d;
+    const int N = P->N, B = d.items;
+    Levels L{};
+    L.nlev = d.num_scales;
+    L.N = N;
+    Levels M = L;   // the mean pass caps blocks per image at 64 per level
+    bool any_two_pass = false;
+    for (int s = 0; s < d.num_scales; ++s) {
+        const bool two_pass = s >= first_level && !P->fused[s];
+        any_two_pass |= two_pass;
+        L.img[s] = P->pyr[s];
+        M.img[s] = two_pass ? P->pyr[s] : nullptr;
+        L.aug[s] = M.aug[s] = color_aug[s];
+        L.hw[s] = M.hw[s] = P->h[s] * P->w[s];
+        const int nb = (int)blocks_for(L.hw[s]);
+        L.first[s + 1] = L.first[s] + nb;
+        M.first[s + 1] = M.first[s] + std::min(nb, 64);
+    }
+    if (any_two_pass)
+        hipLaunchKernelGGL(mean_kernel, dim3(M.first[d.num_scales], N), dim3(kThreads), 0, st, M, B, items, P->sums,
+                           (const int*)nullptr);
+    hipLaunchKernelGGL(apply_kernel, dim3(L.first[d.num_scales], N), dim3(kThreads), 0, st, L, B, items, P->sums);
+}
+
+}  // namespace
+
+extern "C" {
+
+md2_aug_plan* md2_aug_plan_create(const md2_aug_desc* d) {
+    if (!d) return md2_report_error(MD2_ERR_ARG, "aug desc is NULL"), nullptr;
+    const int32_t size[2] = {d->in_height, d->in_width};
+    return plan_build(d, size, 1, false);
+}
+
+md2_aug_plan* md2_aug_plan_create_mixed(const md2_aug_desc* d, const int32_t* sizes, int num_sizes) {
+    if (!d || !sizes) return md2_report_error(MD2_ERR_ARG, "aug: desc/sizes is NULL"), nullptr;
+    if (num_sizes < 1 || num_sizes > kMaxClasses)
+        return md2_report_error(MD2_ERR_ARG, "aug: num_sizes must be 1..16"), nullptr;
+    return plan_build(d, sizes, num_sizes, true);
+}
+
 void md2_aug_plan_destroy(md2_aug_plan* P) {
     if (!P) return;
     for (int r = 0; r < kRing; ++r)
@@ -653,7 +800,7 @@ void md2_aug_plan_destroy(md2_aug_plan* P) {
             (void)hipEventSynchronize(P->staged[r]);
             (void)hipEventDestroy(P->staged[r]);
         }
-    if (P->host_items) (void)hipHostFree(P->host_items);
+    if (P->host_stage) (void)hipHostFree(P->host_stage);
     if (P->block) (void)hipFree(P->block);
     delete P;
 }
@@ -667,15 +814,12 @@ int md2_aug_run2(md2_aug_plan* P, const uint8_t* frames, const md2_aug_item* hos
                  float* const* color_aug, uint32_t* src8, void* stream) {
     if (!P || !frames || !host_items || !color || !color_aug)
         return md2_report_error(MD2_ERR_ARG, "aug: plan/frames/items/color/color_aug is NULL");
+    if (P->mixed) return md2_report_error(MD2_ERR_ARG, "aug: a mixed-size plan runs through md2_aug_run_mixed");
     const md2_aug_desc& d = P->d;
     for (int s = 0; s < d.num_scales; ++s)
         if (!color[s] || !color_aug[s]) return md2_report_error(MD2_ERR_ARG, "aug: color[s]/color_aug[s] is NULL");
-    for (int b = 0; b < d.items; ++b) {
-        const md2_aug_item& it = host_items[b];
-        unsigned seen = 0;
-        for (int k = 0; k < 4; ++k) seen |= it.order[k] < 4 ? 1u << it.order[k] : 16u;
-        if (seen != 15u) return md2_report_error(MD2_ERR_ARG, "aug: items[b].order must be a permutation of 0..3");
-    }
+    if (!orders_ok(host_items, d.items))
+        return md2_report_error(MD2_ERR_ARG, "aug: items[b].order must be a permutation of 0..3");
     hipStream_t st = (hipStream_t)stream;
     const int N = P->N, B = d.items;
     // stage the item parameters: pinned slot -> device slot, asynchronously on `st`
@@ -683,51 +827,106 @@ int md2_aug_run2(md2_aug_plan* P, const uint8_t* frames, const md2_aug_item* hos
     P->slot = (P->slot + 1) % kRing;
     if (hipEventSynchronize(P->staged[r]) != hipSuccess)
         return md2_report_error(MD2_ERR_HIP, "aug: waiting for a staging slot failed");
-    memcpy(P->host_items + (size_t)r * B, host_items, (size_t)B * sizeof(md2_aug_item));
-    const md2_aug_item* items = P->dev_items + (size_t)r * B;
-    if (hipMemcpyAsync((void*)items, P->host_items + (size_t)r * B, (size_t)B * sizeof(md2_aug_item),
-                       hipMemcpyHostToDevice, st) != hipSuccess ||
+    char* host = P->host_stage + (size_t)r * P->slot_bytes;
+    memcpy(host, host_items, (size_t)B * sizeof(md2_aug_item));
+    const md2_aug_item* items = (const md2_aug_item*)(P->dev_stage + (size_t)r * P->slot_bytes);
+    if (hipMemcpyAsync((void*)items, host, (size_t)B * sizeof(md2_aug_item), hipMemcpyHostToDevice, st) !=
+            hipSuccess ||
         hipEventRecord(P->staged[r], st) != hipSuccess)
         return md2_report_error(MD2_ERR_HIP, "aug: staging the item parameters failed");
     if (hipMemsetAsync(P->sums, 0, (size_t)N * d.num_scales * sizeof(unsigned long long), st) != hipSuccess)
         return md2_report_error(MD2_ERR_HIP, "aug: hipMemsetAsync failed");
-    for (int s = 0; s < d.num_scales; ++s) {
-        const uint8_t* src = s ? P->pyr[s - 1] : frames;
-        const md2_aug_item* flip = s ? nullptr : items;
-        if (P->fused[s]) {
-            const dim3 grid((P->w[s] + kTileW - 1) / kTileW, (P->h[s] + kTileH - 1) / kTileH, N);
-            hipLaunchKernelGGL(fused_kernel(P->kx[s], P->ky[s]), grid, dim3(kThreads), P->lds[s].bytes, st, src,
-                               P->pyr[s], color[s], P->sh[s], P->sw[s], P->h[s], P->w[s], P->bx[s], P->wx[s],
-                               P->by[s], P->wy[s], P->lds[s], items, B, s == 0 ? 1 : 0, P->sums + (size_t)s * N,
-                               s == 0 ? src8 : nullptr);
+    for (int s = 0; s < d.num_scales; ++s)
+        launch_level(P, s, s ? P->pyr[s - 1] : frames, items, color[s], src8, st);
+    launch_jitter(P, 0, items, color_aug, st);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? MD2_OK : md2_report_error(MD2_ERR_HIP, hipGetErrorString(e));
+}
+
+int md2_aug_run_mixed(md2_aug_plan* P, const uint8_t* frames_base, uint64_t total_bytes, const int32_t* item_class,
+                      const uint64_t* frame_offset, const md2_aug_item* host_items, float* const* color,
+                      float* const* color_aug, uint32_t* src8, void* stream) {
+    if (!P || !frames_base || !item_class || !frame_offset || !host_items || !color || !color_aug)
+        return md2_report_error(MD2_ERR_ARG,
+                                "aug: plan/frames_base/item_class/frame_offset/items/color/color_aug is NULL");
+    if (!P->mixed) return md2_report_error(MD2_ERR_ARG, "aug: md2_aug_run_mixed needs a mixed-size plan");
+    const md2_aug_desc& d = P->d;
+    for (int s = 0; s < d.num_scales; ++s)
+        if (!color[s] || !color_aug[s]) return md2_report_error(MD2_ERR_ARG, "aug: color[s]/color_aug[s] is NULL");
+    if (!orders_ok(host_items, d.items))
+        return md2_report_error(MD2_ERR_ARG, "aug: items[b].order must be a permutation of 0..3");
+    const int N = P->N, B = d.items;
+    // everything the kernels will index with, checked here (overlapping frames are not:
+    // they are read-only, so an overlap is harmless)
+    int count[kMaxClasses] = {};
+    for (int b = 0; b < B; ++b) {
+        if (item_class[b] < 0 || item_class[b] >= P->ncls)
+            return md2_report_error(MD2_ERR_ARG, "aug: item_class[b] is not a size class of the plan");
+        count[item_class[b]] += d.frames;
+    }
+    for (int n = 0; n < N; ++n) {
+        const SizeClass& C = P->cls[item_class[n % B]];
+        const uint64_t bytes = (uint64_t)C.ih * C.iw * 3;
+        if (frame_offset[n] % 16) return md2_report_error(MD2_ERR_ARG, "aug: frame_offset must be a multiple of 16");
+        if (frame_offset[n] > total_bytes || bytes > total_bytes - frame_offset[n])
+            return md2_report_error(MD2_ERR_ARG, "aug: a frame reaches past total_bytes");
+    }
+    hipStream_t st = (hipStream_t)stream;
+    // stage items, offsets and the per-class image lists: one pinned slot, one upload
+    const int r = P->slot;
+    P->slot = (P->slot + 1) % kRing;
+    if (hipEventSynchronize(P->staged[r]) != hipSuccess)
+        return md2_report_error(MD2_ERR_HIP, "aug: waiting for a staging slot failed");
+    char* host = P->host_stage + (size_t)r * P->slot_bytes;
+    char* dev = P->dev_stage + (size_t)r * P->slot_bytes;
+    memcpy(host, host_items, (size_t)B * sizeof(md2_aug_item));
+    memcpy(host + P->o_offs, frame_offset, (size_t)N * sizeof(uint64_t));
+    int start[kMaxClasses + 1] = {};
+    for (int c = 0; c < P->ncls; ++c) start[c + 1] = start[c] + count[c];
+    int* list = (int*)(host + P->o_list);
+    int fill[kMaxClasses];
+    std::copy(start, start + kMaxClasses, fill);
+    for (int n = 0; n < N; ++n) list[fill[item_class[n % B]]++] = n;   // ascending within a class
+    const md2_aug_item* items = (const md2_aug_item*)dev;
+    const ClassList all{(const unsigned long long*)(dev + P->o_offs), (const int*)(dev + P->o_list)};
+    if (hipMemcpyAsync(dev, host, P->o_list + (size_t)N * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipEventRecord(P->staged[r], st) != hipSuccess)
+        return md2_report_error(MD2_ERR_HIP, "aug: staging the item parameters failed");
+    if (hipMemsetAsync(P->sums, 0, (size_t)N * d.num_scales * sizeof(unsigned long long), st) != hipSuccess)
+        return md2_report_error(MD2_ERR_HIP, "aug: hipMemsetAsync failed");
+    // scale 0: one launch (two on the two-pass route) per size class present
+    const int h0 = P->h[0], w0 = P->w[0];
+    for (int c = 0; c < P->ncls; ++c) {
+        const int cnt = count[c];
+        if (!cnt) continue;
+        const SizeClass& C = P->cls[c];
+        const ClassList cl{all.offs, all.list + start[c]};
+        if (C.fused) {
+            const dim3 grid((w0 + kTileW - 1) / kTileW, (h0 + kTileH - 1) / kTileH, cnt);
+            hipLaunchKernelGGL(fused_kernel_for<true>(C.kx, C.ky), grid, dim3(kThreads), C.lds.bytes, st, frames_base,
+                               P->pyr[0], color[0], C.ih, C.iw, h0, w0, C.bx, C.wx, C.by, C.wy, C.lds, items, B, 1,
+                               P->sums, src8, cl);
         } else {
-            hipLaunchKernelGGL(resize_h_kernel, dim3(blocks_for((size_t)N * P->sh[s] * P->w[s])), dim3(kThreads), 0,
-                               st, src, P->mid, N, P->sh[s], P->sw[s], P->w[s], P->bx[s], P->wx[s], P->kx[s], flip, B);
-            hipLaunchKernelGGL(resize_v_kernel, dim3(blocks_for((size_t)N * P->h[s] * P->w[s])), dim3(kThreads), 0,
-                               st, P->mid, P->pyr[s], N, P->sh[s], P->h[s], P->w[s], P->by[s], P->wy[s], P->ky[s],
-                               color[s], s == 0 ? src8 : nullptr, B);
+            hipLaunchKernelGGL(resize_h_kernel<true>, dim3(blocks_for((size_t)cnt * C.ih * w0)), dim3(kThreads), 0,
+                               st, frames_base, P->mid, cnt, C.ih, C.iw, w0, C.bx, C.wx, C.kx, items, B, cl);
+            hipLaunchKernelGGL(resize_v_kernel<true>, dim3(blocks_for((size_t)cnt * h0 * w0)), dim3(kThreads), 0, st,
+                               P->mid, P->pyr[0], cnt, C.ih, h0, w0, C.by, C.wy, C.ky, color[0], src8, B, cl);
+            // this class's contrast sums (a fused class adds its own inside the kernel)
+            Levels M{};
+            M.nlev = 1;
+            M.N = N;
+            M.img[0] = P->pyr[0];
+            M.hw[0] = h0 * w0;
+            M.first[1] = std::min((int)blocks_for(M.hw[0]), 64);
+            hipLaunchKernelGGL(mean_kernel, dim3(M.first[1], cnt), dim3(kThreads), 0, st, M, B, items, P->sums,
+                               cl.list);
         }
     }
-    Levels L{};
-    L.nlev = d.num_scales;
-    L.N = N;
-    Levels M = L;   // the mean pass caps blocks per image at 64 per level
-    bool any_two_pass = false;
-    for (int s = 0; s < d.num_scales; ++s) {
-        any_two_pass |= !P->fused[s];
-        L.img[s] = P->pyr[s];
-        M.img[s] = P->fused[s] ? nullptr : P->pyr[s];
-        L.aug[s] = M.aug[s] = color_aug[s];
-        L.hw[s] = M.hw[s] = P->h[s] * P->w[s];
-        const int nb = (int)blocks_for(L.hw[s]);
-        L.first[s + 1] = L.first[s] + nb;
-        M.first[s + 1] = M.first[s] + std::min(nb, 64);
-    }
-    if (any_two_pass)
-        hipLaunchKernelGGL(mean_kernel, dim3(M.first[d.num_scales], N), dim3(kThreads), 0, st, M, B, items, P->sums);
-    hipLaunchKernelGGL(apply_kernel, dim3(L.first[d.num_scales], N), dim3(kThreads), 0, st, L, B, items, P->sums);
+    for (int s = 1; s < d.num_scales; ++s) launch_level(P, s, P->pyr[s - 1], items, color[s], nullptr, st);
+    launch_jitter(P, 1, items, color_aug, st);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? MD2_OK : md2_report_error(MD2_ERR_HIP, hipGetErrorString(e));
 }
 
 }  // extern "C"
+

@@ -1,0 +1,271 @@
+"""Batch loader: split lines -> decoded frames in pinned memory -> one upload -> the GPU
+input pipeline -> the dict `Trainer.train_step` / `val_step` take.
+
+Stands where the reference has `DataLoader(dataset, batch_size, shuffle, num_workers,
+pin_memory=True, drop_last=True)` (trainer.py:127-139) around a dataset whose
+`__getitem__` did all the PIL work.  Here the dataset only names and decodes files
+(datasets.py) and the per-item work runs on the GPU for the whole batch
+(augment.GpuAugmentMixed), so a batch is:
+
+  1. the epoch's permutation (drawn from `seed` and the epoch), cut into batches with the
+     last partial one dropped, batches dealt to ranks as `rank::world_size`;
+  2. every image file of the batch opened (sizes are known from the headers), frame
+     offsets laid out 256-byte aligned in one ragged buffer;
+  3. the frames decoded by up to min(num_workers, 16) THREADS (PIL releases the GIL while
+     it decodes; no process is forked or spawned beside one that has the GPU open) and
+     copied into one of a small ring of pinned buffers;
+  4. one asynchronous host-to-device copy of that buffer and one `GpuAugmentMixed` call.
+
+Steps 2-3 of the next `prefetch` batches run on a producer thread while the caller trains
+on the current one.  That thread and the decoding threads do host work only: every call
+into the HIP runtime (allocating the pinned ring, uploads, events and waiting for them) is
+made on the caller's thread, between its steps, so none can fall into a graph capture the
+caller has open on another stream (a host allocation from a second thread is refused
+while a global-mode capture runs).  The ring is allocated when an epoch starts, sized from
+its first batch with an eighth to spare; a later batch that needs more is decoded into
+pageable memory and its slot grown on the caller's thread.  A pinned buffer goes back to
+the producer only after the event recorded behind its upload has completed, two batches
+later; nothing here calls torch.cuda.synchronize().
+"""
+from __future__ import annotations
+
+import collections
+import queue
+import random
+import threading
+from concurrent.futures import ThreadPoolExecutor
+from typing import Dict, Iterator, List, Optional
+
+import numpy as np
+import torch
+
+from .augment import GpuAugmentMixed
+from .datasets import item_seed
+
+ALIGN = 256        # frame offsets in the ragged buffer
+MAX_THREADS = 16   # decoding threads, whatever --num_workers asks for
+IN_FLIGHT = 2      # uploads that may still be running when a batch is handed out
+
+
+def _padded(size) -> int:
+    return (size[0] * size[1] * 3 + ALIGN - 1) // ALIGN * ALIGN
+
+
+class _Staged:
+    """A batch decoded into ring slot `slot`, ready for its upload.  `spill`: the frames
+    in pageable memory, where the slot's pinned buffer was too small for them."""
+
+    def __init__(self, slot, total, offsets, items, spill=None):
+        self.slot, self.total, self.offsets, self.items, self.spill = slot, total, offsets, items, spill
+
+
+class BatchLoader:
+    def __init__(self, dataset, batch_size: int, shuffle: bool = True, seed: int = 0, num_workers: int = 0,
+                 rank: int = 0, world_size: int = 1, device=None, with_depth: bool = False, prefetch: int = 2):
+        if not (0 <= rank < world_size):
+            raise ValueError(f"rank {rank} outside world size {world_size}")
+        self.dataset = dataset
+        self.batch_size = batch_size
+        self.shuffle = shuffle
+        self.seed = seed
+        self.threads = min(max(int(num_workers), 0), MAX_THREADS)
+        self.rank, self.world_size = rank, world_size
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        if self.device.type != "cuda":
+            raise RuntimeError("BatchLoader feeds the GPU input pipeline (no CPU fallback)")
+        if with_depth and not getattr(dataset, "load_depth", False):
+            raise ValueError("with_depth needs a dataset built with load_depth=True whose first split line has "
+                             "ground truth (check_depth)")
+        self.with_depth = with_depth
+        self.prefetch = max(int(prefetch), 1)
+        self.epoch = 0
+        self.frame_ids = list(dataset.frame_idxs)
+        self.aug = GpuAugmentMixed(dataset.height, dataset.width, self.frame_ids, batch_size, dataset.num_scales,
+                                   device=self.device)
+        # ring: one slot being filled, `prefetch` queued, IN_FLIGHT whose upload may be running
+        self._ring = self.prefetch + 1 + IN_FLIGHT
+        self._pinned: List[Optional[torch.Tensor]] = [None] * self._ring
+        self._uploaded: List[Optional[torch.cuda.Event]] = [None] * self._ring
+        self._pool = ThreadPoolExecutor(self.threads, thread_name_prefix="md2-decode") if self.threads else None
+
+    # ------------------------------------------------------------------ order
+    def set_epoch(self, epoch: int):
+        self.epoch = int(epoch)
+
+    def batches(self, epoch: Optional[int] = None) -> List[List[int]]:
+        """This rank's batches of dataset indices for `epoch`."""
+        epoch = self.epoch if epoch is None else epoch
+        order = list(range(len(self.dataset)))
+        if self.shuffle:
+            random.Random(item_seed(self.seed, epoch, -1)).shuffle(order)
+        B = self.batch_size
+        full = [order[i * B:(i + 1) * B] for i in range(len(order) // B)]   # drop_last
+        per_rank = len(full) // self.world_size                             # equal steps on every rank
+        return full[self.rank::self.world_size][:per_rank]
+
+    def __len__(self):
+        return (len(self.dataset) // self.batch_size) // self.world_size
+
+    # ---------------------------------------------------------------- staging
+    def _map(self, fn, seq):
+        return list(self._pool.map(fn, seq)) if self._pool is not None else [fn(x) for x in seq]
+
+    def _open(self, indices: List[int], epoch: int):
+        """Step 2: the batch's items with their image files open.  If one item fails, the
+        files of the others are closed before its error is raised."""
+        def one(i):
+            try:
+                return self.dataset.open_item(i, epoch)
+            except BaseException as e:
+                return e
+
+        items = self._map(one, indices)
+        errors = [it for it in items if isinstance(it, BaseException)]
+        if errors:
+            for it in items:
+                if not isinstance(it, BaseException):
+                    it.close()
+            raise errors[0]
+        return items
+
+    def _stage(self, indices: List[int], epoch: int, slot: int) -> _Staged:
+        """Steps 2-3 for one batch into the free ring slot `slot`: host work only."""
+        items = self._open(indices, epoch)
+        try:
+            F, B = len(self.frame_ids), len(items)
+            offsets, total = [0] * (F * B), 0
+            for f in range(F):
+                for b, it in enumerate(items):
+                    offsets[f * B + b] = total
+                    total += _padded(it.size)
+            buf, spill = self._pinned[slot], None
+            if buf is None or buf.numel() < total:
+                host = spill = np.empty(total, dtype=np.uint8)
+            else:
+                host = buf.numpy()
+
+            def decode(n):
+                arr = self.dataset.decode(items[n % B].images[n // B])
+                host[offsets[n]:offsets[n] + arr.size] = arr.reshape(-1)
+
+            self._map(decode, range(F * B))
+        finally:
+            for it in items:
+                it.close()
+        return _Staged(slot, total, offsets, items, spill)
+
+    def _reserve(self, slot: int, total: int):
+        """Slot `slot`'s pinned buffer holds `total` bytes (caller's thread; the slot is free)."""
+        buf = self._pinned[slot]
+        if buf is None or buf.numel() < total:
+            self._pinned[slot] = torch.empty(total + total // 8, dtype=torch.uint8, pin_memory=True)
+
+    def _finish(self, st: _Staged) -> Dict:
+        """Step 4, on the caller's thread and stream."""
+        with torch.cuda.device(self.device):
+            if st.spill is not None:
+                self._reserve(st.slot, st.total)
+                self._pinned[st.slot].numpy()[:st.total] = st.spill
+            dev = torch.empty(st.total, dtype=torch.uint8, device=self.device)
+            dev.copy_(self._pinned[st.slot][:st.total], non_blocking=True)
+            if self._uploaded[st.slot] is None:
+                self._uploaded[st.slot] = torch.cuda.Event()
+            self._uploaded[st.slot].record()
+            draws = [it.draw for it in st.items]
+            sides = [it.side for it in st.items] if "s" in self.frame_ids else None
+            inputs = self.aug(dev, [it.size for it in st.items], st.offsets, draws, sides)
+            if self.with_depth:
+                inputs["depth_gt"] = self.dataset.get_depths(st.items, device=self.device).unsqueeze(1)
+        return inputs
+
+    # -------------------------------------------------------------- iteration
+    def __iter__(self) -> Iterator[Dict]:
+        epoch = self.epoch
+        todo = self.batches(epoch)
+        if not todo:
+            self.epoch = epoch + 1
+            return
+        # every slot is free once the uploads of an earlier epoch have run; the ring is
+        # sized here, before the producer starts, from the first batch's headers
+        first = self._open(todo[0], epoch)
+        for it in first:
+            it.close()
+        need = len(self.frame_ids) * sum(_padded(it.size) for it in first)
+        free: "queue.Queue" = queue.Queue()
+        for slot in range(self._ring):
+            if self._uploaded[slot] is not None:
+                self._uploaded[slot].synchronize()
+            self._reserve(slot, need)
+            free.put(slot)
+        in_flight = collections.deque()   # slots behind an upload, oldest first
+
+        def retire():
+            while len(in_flight) >= IN_FLIGHT:
+                slot = in_flight.popleft()
+                self._uploaded[slot].synchronize()   # its upload has run: the producer may refill it
+                free.put(slot)
+
+        if self._pool is None:   # no threads: everything on the caller's thread
+            for indices in todo:
+                retire()
+                st = self._stage(indices, epoch, free.get_nowait())
+                out = self._finish(st)
+                in_flight.append(st.slot)
+                yield out
+            self.epoch = epoch + 1
+            return
+        ready: "queue.Queue" = queue.Queue(maxsize=self.prefetch)
+        stop = threading.Event()
+
+        def put(obj):
+            while not stop.is_set():
+                try:
+                    ready.put(obj, timeout=0.1)
+                    return
+                except queue.Full:
+                    pass
+
+        def take():
+            while not stop.is_set():
+                try:
+                    return free.get(timeout=0.1)
+                except queue.Empty:
+                    pass
+            return None
+
+        def produce():   # host work only: no call into the HIP runtime on this thread
+            try:
+                for indices in todo:
+                    slot = take()
+                    if slot is None:
+                        return
+                    put(self._stage(indices, epoch, slot))
+            except BaseException as e:   # handed to the consumer
+                put(e)
+
+        producer = threading.Thread(target=produce, name="md2-loader", daemon=True)
+        producer.start()
+        try:
+            for _ in todo:
+                retire()
+                st = ready.get()
+                if isinstance(st, BaseException):
+                    raise st
+                out = self._finish(st)
+                in_flight.append(st.slot)
+                yield out
+            self.epoch = epoch + 1
+        finally:
+            stop.set()
+            producer.join()
+
+    def close(self):
+        if self._pool is not None:
+            self._pool.shutdown(wait=True)
+            self._pool = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -75,6 +75,9 @@ _FLAGS = [
     ("--gt_poses", dict(type=str, help="build: KITTI poses file (12 numbers per line) for evaluate_pose; default "
                                        "<data_path>/poses/NN.txt")),
     ("--ext_poses_to_eval", dict(type=str, help="build: external poses.npy (N,4,4) float32 for evaluate_pose")),
+    ("--split_dir", dict(type=str, help="build: folder holding train_files.txt and val_files.txt for train; "
+                                        "default splits/<split>/ beside the package (the lists are not shipped)")),
+    ("--seed", dict(type=int, default=0, help="build: seed of the loader's shuffle and of the per-item draws")),
     # build-specific
     ("--materialize_images", dict(action="store_true",
                                   help="build: also materialise warped colours/samples/depth every step")),

@@ -698,6 +698,72 @@ class Trainer:
         self.epoch += 1
         self._agree_conv_choices(again=True)
 
+    def train(self, train_loader, val_loader=None):
+        """The whole training run (trainer.py:182-226): num_epochs epochs over
+        `train_loader`, the reference's early / late logging rule, on a log step log_time,
+        one val_step on the next validation batch (the iterator restarts when exhausted)
+        and the scalars of both, a checkpoint every save_frequency epochs.  Reading the
+        losses on a log step is the only host synchronisation this adds to train_step.
+        The reference calls scheduler.step() at the start of an epoch (the convention of
+        its torch); here it steps after each epoch, as run_epoch does.
+        With several ranks every rank runs the same steps (the training step holds the
+        gradient exchange), but only rank 0 prints and writes: opt.json, the scalars and the checkpoints are
+        one set of files that every rank would otherwise open at once.  Nothing in the
+        run reads them back, so no barrier follows a save."""
+        if self.rank == 0:
+            self.save_opts()
+        self.start_time = time.time()
+        self._val_iter = None
+        first = self.epoch
+        for epoch in range(first, self.opt.num_epochs):
+            self.epoch = epoch
+            self.set_train()
+            if hasattr(train_loader, "set_epoch"):
+                train_loader.set_epoch(epoch)
+            for batch_idx, inputs in enumerate(train_loader):
+                t0 = time.time()
+                step = self.step   # train_step advances it; the rule reads it before (trainer.py:214-226)
+                outputs, losses = self.train_step(inputs)
+                early_phase = batch_idx % self.opt.log_frequency == 0 and step < 2000
+                late_phase = step % 2000 == 0
+                if early_phase or late_phase:
+                    scalars = {k: float(v.detach()) for k, v in losses.items() if torch.is_tensor(v) and v.numel() == 1}
+                    if self.rank == 0:
+                        self.log_time(batch_idx, time.time() - t0, scalars["loss"])
+                    self.log_scalars("train", step, scalars)
+                    if val_loader is not None:
+                        self.log_scalars("val", step, self.val(val_loader))
+            self.model_lr_scheduler.step()
+            self._agree_conv_choices(again=True)
+            if (epoch + 1) % self.opt.save_frequency == 0 and self.rank == 0:
+                self.save_model()   # weights_{epoch}, as the reference names them
+        self.epoch = max(self.opt.num_epochs, first)
+        if self._val_iter is not None and hasattr(self._val_iter, "close"):
+            self._val_iter.close()   # a loader's iterator owns a producer thread
+        self._val_iter = None
+
+    def val(self, val_loader):
+        """trainer.py:211-226: one validation batch, its scalars read back."""
+        if self._val_iter is None:
+            self._val_iter = iter(val_loader)
+        try:
+            inputs = next(self._val_iter)
+        except StopIteration:
+            self._val_iter = iter(val_loader)
+            inputs = next(self._val_iter)
+        _, losses = self.val_step(inputs)
+        return {k: float(v.detach()) for k, v in losses.items() if torch.is_tensor(v) and v.numel() == 1}
+
+    def log_scalars(self, mode: str, step: int, scalars: Dict[str, float]):
+        """One JSON object per log step in <log_path>/<mode>/scalars.jsonl (the reference
+        writes tensorboard events, trainer.py:546-551; images are not logged)."""
+        if self.rank != 0:
+            return
+        folder = os.path.join(self.log_path, mode)
+        os.makedirs(folder, exist_ok=True)
+        with open(os.path.join(folder, "scalars.jsonl"), "a") as f:
+            f.write(json.dumps({"step": step, "epoch": self.epoch, **scalars}) + "\n")
+
     def val_step(self, inputs):
         """One validation batch (trainer.py:211-226 val()): the networks in eval mode under
         no_grad, the losses, and with inputs["depth_gt"] the seven depth metrics of

@@ -1,0 +1,157 @@
+"""Input pipeline timing: the mixed-size augment against the single-size one, and the
+batch loader end to end on JPEG files (informational, like tools/velo_bench.py).
+
+    python tools/loader_bench.py [--batch 12] [--repeats 5] [--calls 20] [--frames 160]
+                                 [--threads 1 8 16] [--out profiles/loader_bench.json]
+
+augment   md2_aug_run_mixed on --batch items x 3 frames that mix KITTI raw's four decoded
+          sizes (375x1242, 370x1226, 374x1238, 376x1241, a quarter of the items each)
+          against md2_aug_run2 of a single-size plan on --batch x 3 frames of 375x1242,
+          both to the 192x640 four-level pyramid with mixed draws; frames resident on the
+          device.  HIP events around --calls calls, alternating the two, one warm-up
+          each, the median of --repeats.
+loader    loader.BatchLoader over a synthetic KITTI-raw tree (four drives, one per size,
+          --frames JPEG frames each, written with PIL at quality 92 from textured noise),
+          frame ids [0, -1, 1], shuffled, decoded by 1 / 8 / 16 threads: wall time of one
+          whole epoch, through the last batch's device synchronise, one warm-up epoch, the
+          median of --repeats; frames per second = decoded JPEG files per second.
+
+Prints one JSON line; --out also writes it to a file.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import platform
+import random
+import statistics
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+from PIL import Image
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from monodepth2_amd.augment import GpuAugment, GpuAugmentMixed, draw_item, pack_items, pack_ragged  # noqa: E402
+from monodepth2_amd.datasets import KITTIRAWDataset  # noqa: E402
+from monodepth2_amd.loader import BatchLoader  # noqa: E402
+
+SIZES = [(375, 1242), (370, 1226), (374, 1238), (376, 1241)]
+H, W, S = 192, 640, 4
+FRAME_IDS = [0, -1, 1]
+
+
+def texture(rng, h, w):
+    yy, xx = np.mgrid[0:h, 0:w]
+    base = np.zeros((h, w, 3))
+    for _ in range(6):
+        k = rng.uniform(0.005, 0.05, 2)
+        base += rng.uniform(20, 60) * np.sin(k[0] * xx + k[1] * yy + rng.uniform(0, 6.3))[..., None] \
+            * rng.uniform(0.3, 1.0, 3)
+    base += 128 + rng.normal(0, 12, base.shape)
+    return np.clip(base, 0, 255).astype(np.uint8)
+
+
+def bench_augment(batch, calls, repeats):
+    rng = np.random.default_rng(0)
+    draws = [draw_item(random.Random(i)) for i in range(batch)]
+    items = pack_items(draws)
+    F = len(FRAME_IDS)
+    one = [texture(rng, h, w) for h, w in SIZES]
+    mixed_frames = [[one[b % len(SIZES)] for b in range(batch)] for _ in range(F)]
+    buf, offs, sizes = pack_ragged(mixed_frames)
+    ragged = torch.from_numpy(buf).cuda()
+    dense = torch.from_numpy(np.broadcast_to(one[0], (F, batch) + one[0].shape).copy()).cuda()
+    mixed = GpuAugmentMixed(H, W, FRAME_IDS, batch, S, sizes=SIZES)
+    single = GpuAugment(H, W, SIZES[0][0], SIZES[0][1], FRAME_IDS, batch, S)
+    runs = {"mixed": lambda: mixed.run(ragged, sizes, offs, items), "single": lambda: single.run(dense, items)}
+    times = {k: [] for k in runs}
+    for fn in runs.values():
+        fn()
+    torch.cuda.synchronize()
+    for _ in range(repeats):
+        for name, fn in runs.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(calls):
+                fn()
+            b.record()
+            b.synchronize()
+            times[name].append(a.elapsed_time(b) / calls)
+    med = {k: statistics.median(v) for k, v in times.items()}
+    return {"batch": batch, "frames": F, "calls": calls, "mixed_ms": med["mixed"], "single_ms": med["single"],
+            "ratio": med["mixed"] / med["single"], "mixed_ms_all": times["mixed"], "single_ms_all": times["single"],
+            "classes_present": len(set(sizes))}
+
+
+def write_tree(root, frames):
+    rng = np.random.default_rng(1)
+    lines = []
+    for n, (h, w) in enumerate(SIZES):
+        drive = "2011_09_{:02d}/2011_09_{:02d}_drive_0001_sync".format(26 + n, 26 + n)
+        folder = os.path.join(root, drive, "image_02/data")
+        os.makedirs(folder)
+        base = [texture(rng, h, w) for _ in range(4)]
+        for f in range(frames):
+            Image.fromarray(np.roll(base[f % 4], 3 * f, axis=1)).save(
+                os.path.join(folder, "{:010d}.jpg".format(f)), quality=92)
+        lines += ["{} {} l".format(drive, f) for f in range(1, frames - 1)]
+    return lines
+
+
+def bench_loader(batch, frames, threads_list, repeats):
+    out = {}
+    with tempfile.TemporaryDirectory() as root:
+        lines = write_tree(root, frames)
+        size = sum(os.path.getsize(os.path.join(dp, f)) for dp, _, fs in os.walk(root) for f in fs)
+        ds = KITTIRAWDataset(root, lines, H, W, FRAME_IDS, S, is_train=True, img_ext=".jpg")
+        for threads in threads_list:
+            ld = BatchLoader(ds, batch, shuffle=True, seed=0, num_workers=threads)
+            times = []
+            for rep in range(repeats + 1):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                n = 0
+                for batch_inputs in ld:
+                    n += 1
+                torch.cuda.synchronize()
+                if rep:
+                    times.append(time.perf_counter() - t0)
+            ld.close()
+            t = statistics.median(times)
+            out[str(threads)] = {"epoch_s": t, "batches": n, "frames_per_s": n * batch * len(FRAME_IDS) / t,
+                                 "items_per_s": n * batch / t, "epoch_s_all": times}
+        out["files"] = len(SIZES) * frames
+        out["mean_file_bytes"] = size / (len(SIZES) * frames)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=12)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--calls", type=int, default=20)
+    ap.add_argument("--frames", type=int, default=160)
+    ap.add_argument("--threads", type=int, nargs="+", default=[1, 8, 16])
+    ap.add_argument("--out", type=str)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("loader_bench needs a GPU: nothing here is timed on the host alone")
+    res = {"tool": "loader_bench", "device": torch.cuda.get_device_name(0),
+           "python": platform.python_version(), "pillow": Image.__version__,
+           "augment": bench_augment(args.batch, args.calls, args.repeats),
+           "loader": bench_loader(args.batch, args.frames, args.threads, args.repeats)}
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
