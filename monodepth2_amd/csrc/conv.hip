@@ -34,13 +34,14 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "md2_x6.h"
 #include "md2hot.h"
 
 int md2_report_error(int code, const char* msg);
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using namespace md2;   // md2_x6.h: the split-bf16 format, md2_bf16.h: f2bf / bf16_round
 
 constexpr int kThreads = 256;
 constexpr int BM = 128;         // tile rows (M)
@@ -87,12 +88,6 @@ struct ConvArgs {
     int ybf16;
 };
 
-__device__ __forceinline__ int xcd_contiguous_block(int bid, int n) {
-    const int q = n >> 3, r = n & 7;
-    const int xcd = bid & 7, idx = bid >> 3;
-    return xcd < r ? xcd * (q + 1) + idx : r * (q + 1) + (xcd - r) * q + idx;
-}
-
 __device__ __forceinline__ float4 bload(__amdgpu_buffer_rsrc_t r, int byte_off) {
     return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0));
 }
@@ -102,15 +97,6 @@ constexpr int kBad = 0x7fffffff;   // a byte offset past every buffer: the load 
 // 8 bytes (four bf16) from a buffer
 __device__ __forceinline__ uint2 bload8(__amdgpu_buffer_rsrc_t r, int byte_off) {
     return __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(r, byte_off, 0, 0));
-}
-// fp32 -> bf16 bits, round to nearest even (finite values; NaN stays a NaN)
-__device__ __forceinline__ uint16_t f2bf16(float v) {
-    const uint32_t u = __builtin_bit_cast(uint32_t, v);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
-    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-__device__ __forceinline__ float bf16_round(float v) {
-    return __builtin_bit_cast(float, (uint32_t)f2bf16(v) << 16);
 }
 
 // n / d for 0 <= n < 2^24, d >= 1, from a float reciprocal (rd = 1.0f / d) and one
@@ -371,8 +357,9 @@ __global__ __launch_bounds__(kThreads, BN == 128 ? 2 : (BN == 64 ? 3 : 4)) void 
 
 // ----------------------------------------------------------------------------
 // Split-bf16 ("x6") forward: f32 operands split exactly into three bf16 planes
-// (x = x0 + x1 + x2: 8 + 8 + 8 significand bits = all 24 of an f32; see split3), products by v_mfma_f32_32x32x16_bf16 keeping the six terms xi*yj with
-// i + j <= 2 (the three dropped ones are below 2^-24 relative), f32 accumulation.
+// (x = x0 + x1 + x2: 8 + 8 + 8 significand bits = all 24 of an f32), products by
+// v_mfma_f32_32x32x16_bf16 keeping the six terms xi*yj with i + j <= 2, f32
+// accumulation — md2_x6.h defines the split, the plane layout and the product order.
 // Error per product <= ~3 * 2^-24 relative: f32-class accuracy (tests compare it
 // with the exact-f32 MFMA path against an fp64 reference) at 6 bf16 MFMAs of 32
 // cycles per 16 k instead of 8 f32 MFMAs of 64 cycles: 2.7x the MFMA rate.
@@ -380,57 +367,6 @@ __global__ __launch_bounds__(kThreads, BN == 128 ? 2 : (BN == 64 ? 3 : 4)) void 
 // from f32 registers (split on the way) into LDS planes [row][32 k] bf16 whose 16-byte
 // quads are XOR-swizzled by (row >> 2) & 3 (conflict-free ds_read_b128 fragments).
 // ----------------------------------------------------------------------------
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-constexpr int XBK = 32;
-
-// Exact three-way split by truncation: x0 = x with the low 16 bits cleared (the top 8
-// significand bits), r1 = x - x0 exact (<= 16 significant bits), x1 = r1 truncated the
-// same way, x2 = r1 - x1 exact with <= 8 significant bits, so its bf16 (the high half)
-// is exact too: x == x0 + x1 + x2.  Pairs of elements are packed with one v_perm per
-// plane (the high halves of two dwords).
-__device__ __forceinline__ uint32_t hi16x2(float lo, float hi) {
-    return __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, hi), __builtin_bit_cast(uint32_t, lo), 0x07060302u);
-}
-__device__ __forceinline__ float trunc16(float x) {
-    return __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, x) & 0xFFFF0000u);
-}
-__device__ __forceinline__ void split3(float4 v, bf16x4& p0, bf16x4& p1, bf16x4& p2) {
-    const float x[4] = {v.x, v.y, v.z, v.w};
-    float a[4], b[4], c[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        a[i] = trunc16(x[i]);
-        const float r1 = x[i] - a[i];
-        b[i] = trunc16(r1);
-        c[i] = r1 - b[i];
-    }
-    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-    u32x2 q0, q1, q2;
-    q0.x = hi16x2(a[0], a[1]), q0.y = hi16x2(a[2], a[3]);
-    q1.x = hi16x2(b[0], b[1]), q1.y = hi16x2(b[2], b[3]);
-    q2.x = hi16x2(c[0], c[1]), q2.y = hi16x2(c[2], c[3]);
-    p0 = __builtin_bit_cast(bf16x4, q0);
-    p1 = __builtin_bit_cast(bf16x4, q1);
-    p2 = __builtin_bit_cast(bf16x4, q2);
-}
-
-// element index of (row r, k) in a [rows][32] bf16 plane, 16-byte quads swizzled
-__device__ __forceinline__ int xidx(int r, int k) { return r * XBK + ((((k >> 3) ^ (r >> 2)) & 3) << 3) + (k & 7); }
-// xidx with rows r and r ^ 1 swapped in every odd row quad: the same ds_read_b128
-// banks as xidx (a fragment group's rows map onto the same row set), and an 8-byte
-// store of row 4 q + j by the 16 lanes of two quads (q, q + 1) then lands on both
-// 16-bank halves (row parity differs) instead of two-way on one
-__device__ __forceinline__ int xidx2(int r, int k) { return xidx(r ^ ((r >> 2) & 1), k); }
-// The 16x16x32 MFMA path's operand layout: k-octet slot kq ^ (row >> 2 & 2).  Its
-// ds_read_b128 lane groups ({0-3, 12-15, 20-27}, ...) read rows c, 12 + c at one octet
-// and 4 + c, 8 + c at the next, which xidx's kq ^ (row >> 2) puts on the same 16-byte
-// bank slot (two-way on every fragment read); this slot function keeps all four apart.
-template <int MT>
-__device__ __forceinline__ int xsw(int r, int k) {
-    if constexpr (MT == 32) return xidx(r, k);
-    return r * XBK + ((((k >> 3) ^ ((r >> 2) & 2)) & 3) << 3) + (k & 7);
-}
 
 // Weights split once per call into three bf16 planes [3][R][KT][Ck] in row-k order:
 // forward R = Co, Ck = Ci (w as is); input gradient R = Ci, Ck = Co with the taps
@@ -447,10 +383,7 @@ __global__ __launch_bounds__(256) void conv_wsplit_kernel(const float* w, __bf16
         const int co = i % Co, rest = i / Co, t = rest % KT, ci = rest / KT;   // out [ci][t][co]
         v = w[((size_t)co * KT + (KT - 1 - t)) * Ci + ci];
     }
-    const float a = trunc16(v), r1 = v - a, b = trunc16(r1), c = r1 - b;
-    out[i] = __builtin_bit_cast(__bf16, (uint16_t)(__builtin_bit_cast(uint32_t, a) >> 16));
-    out[n + i] = __builtin_bit_cast(__bf16, (uint16_t)(__builtin_bit_cast(uint32_t, b) >> 16));
-    out[2 * n + i] = __builtin_bit_cast(__bf16, (uint16_t)(__builtin_bit_cast(uint32_t, c) >> 16));
+    split_store(out, n, i, v);
 }
 
 // Both layouts in one launch (md2_conv_split_weights): one block per (tap, 32 co,
@@ -458,12 +391,6 @@ __global__ __launch_bounds__(256) void conv_wsplit_kernel(const float* w, __bf16
 // planes [3][Co][KT][Ci] (same element order), and — if `dg` is non-null — transposed
 // through LDS into the input gradient's [3][Ci][KT][Co] with the tap flipped, so
 // those 2-byte stores coalesce along co as well.
-__device__ __forceinline__ void split_store(__bf16* out, int n, int i, float v) {
-    const float a = trunc16(v), r1 = v - a, b = trunc16(r1), c = r1 - b;
-    out[i] = __builtin_bit_cast(__bf16, (uint16_t)(__builtin_bit_cast(uint32_t, a) >> 16));
-    out[n + i] = __builtin_bit_cast(__bf16, (uint16_t)(__builtin_bit_cast(uint32_t, b) >> 16));
-    out[2 * n + i] = __builtin_bit_cast(__bf16, (uint16_t)(__builtin_bit_cast(uint32_t, c) >> 16));
-}
 // A 32 (co) x 32 (ci) tile of one tap, split into the three bf16 planes of the
 // forward layout [co][tap][ci] and (through LDS) of the input-gradient layout
 // [ci][flipped tap][co] / the col layout [tap][ci][co].  With Ci and Co multiples of 4
@@ -474,10 +401,9 @@ __device__ __forceinline__ void split_store(__bf16* out, int n, int i, float v) 
 // bf (MD2_CONV_BF16, md2_conv_bf16_weights): ONE plane per layout, the weight rounded to
 // bf16 (nearest even) — the operand a bf16 autocast convolution multiplies
 __device__ __forceinline__ bf16x4 rne4(float4 v) {
-    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
     u32x2 q;
-    q.x = (uint32_t)f2bf16(v.x) | ((uint32_t)f2bf16(v.y) << 16);
-    q.y = (uint32_t)f2bf16(v.z) | ((uint32_t)f2bf16(v.w) << 16);
+    q.x = f2bf(v.x) | (f2bf(v.y) << 16);
+    q.y = f2bf(v.z) | (f2bf(v.w) << 16);
     return __builtin_bit_cast(bf16x4, q);
 }
 __device__ __forceinline__ void planes_store4(__bf16* out, int n, int i, float4 v, bool bf) {
@@ -587,16 +513,6 @@ struct X6Geo {
     static constexpr int MINB = (BN <= 64 && BMX == 128) ? 2 : 1;
 };
 
-// Workgroup barrier that leaves LDS-DMA loads in flight: __syncthreads()'s fence
-// would wait for every outstanding vector-memory op (vmcnt(0)) once LDS-DMA is in
-// the kernel, draining the register prefetch of A; the DMA is ordered by explicit
-// wait_vm<> calls instead.  The "memory" clobber keeps LDS accesses on their side.
-__device__ __forceinline__ void lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-template <int VM>
-__device__ __forceinline__ void wait_vm() {
-    static_assert(VM >= 0 && VM < 64, "vmcnt");
-    __builtin_amdgcn_s_waitcnt((VM & 0xF) | ((VM >> 4) << 14) | (0x7 << 4) | (0xF << 8));
-}
 // 16 bytes per lane from the buffer at byte offset `voff` into LDS at lds + 16·lane
 // (lds wave-uniform; an offset past the buffer writes zeros)
 __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, void* lds, int voff) {
@@ -796,16 +712,7 @@ __global__ __launch_bounds__((X6Geo<BN, BMX>::NT), (X6Geo<BN, BMX>::MINB)) void 
                 const int e = xsw<16>(wm * (TM * 16) + 16 * i + l16, 8 * kq);
 #pragma unroll
                 for (int pl = 0; pl < NP; ++pl) fa[pl] = *(const bf16x8*)(L + pl * PA + e);
-                if constexpr (BF) {
-                    acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], fb[0], acc[i], 0, 0, 0);
-                } else {
-                    acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[2], fb[0], acc[i], 0, 0, 0);
-                    acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[1], fb[1], acc[i], 0, 0, 0);
-                    acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], fb[2], acc[i], 0, 0, 0);
-                    acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[1], fb[0], acc[i], 0, 0, 0);
-                    acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], fb[1], acc[i], 0, 0, 0);
-                    acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], fb[0], acc[i], 0, 0, 0);
-                }
+                acc[i] = x6_mma16<NP>(fa, fb, acc[i]);
             }
         } else {
 #pragma unroll
@@ -820,17 +727,7 @@ __global__ __launch_bounds__((X6Geo<BN, BMX>::NT), (X6Geo<BN, BMX>::MINB)) void 
                     const int e = xidx(wm * (TM * 32) + 32 * i + lr, 16 * s + 8 * h);
 #pragma unroll
                     for (int pl = 0; pl < NP; ++pl) fa[pl] = *(const bf16x8*)(L + pl * PA + e);
-                    if constexpr (BF) {
-                        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[0], acc[i], 0, 0, 0);
-                    } else {
-                        // small terms first: x2y0, x1y1, x0y2, x1y0, x0y1, x0y0
-                        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[2], fb[0], acc[i], 0, 0, 0);
-                        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[1], acc[i], 0, 0, 0);
-                        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[2], acc[i], 0, 0, 0);
-                        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[0], acc[i], 0, 0, 0);
-                        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[1], acc[i], 0, 0, 0);
-                        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[0], acc[i], 0, 0, 0);
-                    }
+                    acc[i] = x6_mma32<NP>(fa, fb, acc[i]);
                 }
             }
         }
@@ -885,7 +782,7 @@ __global__ __launch_bounds__((X6Geo<BN, BMX>::NT), (X6Geo<BN, BMX>::MINB)) void 
     // BF without a K split: the bf16 output itself (round to nearest even)
     const bool obf = BF && a.ybf16 == 1 && a.splits == 1;
     auto put = [&](int m, int n, float v) {
-        if (obf) ((uint16_t*)a.y)[orow(m) * a.N + n] = f2bf16(v);
+        if (obf) ((uint16_t*)a.y)[orow(m) * a.N + n] = (uint16_t)f2bf(v);
         else out[orow(m) * a.N + n] = v;
     };
     if constexpr (G::MT == 16) {
@@ -1047,15 +944,7 @@ __global__ __launch_bounds__(512, 1) void conv_x6ws_kernel(ConvArgs a) {
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl) fa[pl] = *(const bf16x8*)(L + pl * PA + e);
 #pragma unroll
-                for (int jn = 0; jn < TNc; ++jn) {
-                    // small terms first: x2y0, x1y1, x0y2, x1y0, x0y1, x0y0 (conv_x6_kernel's order)
-                    acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[2], fb[jn][0], acc[i][jn], 0, 0, 0);
-                    acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[jn][1], acc[i][jn], 0, 0, 0);
-                    acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[jn][2], acc[i][jn], 0, 0, 0);
-                    acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[jn][0], acc[i][jn], 0, 0, 0);
-                    acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[jn][1], acc[i][jn], 0, 0, 0);
-                    acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[jn][0], acc[i][jn], 0, 0, 0);
-                }
+                for (int jn = 0; jn < TNc; ++jn) acc[i][jn] = x6_mma32<3>(fa, fb[jn], acc[i][jn]);
             }
         }
     };
@@ -1262,17 +1151,7 @@ __global__ __launch_bounds__((X6Geo<BN, BMX>::NT), 1) void conv_x6p_kernel(ConvA
                                        : xidx(abase[i] + toff, 16 * s + 8 * h);
 #pragma unroll
                 for (int pl = 0; pl < NP; ++pl) fa[pl] = *(const bf16x8*)(lds + pl * PA + e);
-                if constexpr (BF) {
-                    acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[0], acc[i], 0, 0, 0);
-                    continue;
-                } else {
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[2], fb[0], acc[i], 0, 0, 0);
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[1], acc[i], 0, 0, 0);
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[2], acc[i], 0, 0, 0);
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[0], acc[i], 0, 0, 0);
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[1], acc[i], 0, 0, 0);
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[0], acc[i], 0, 0, 0);
-                }
+                acc[i] = x6_mma32<NP>(fa, fb, acc[i]);
             }
         }
     };
@@ -1318,7 +1197,7 @@ __global__ __launch_bounds__((X6Geo<BN, BMX>::NT), 1) void conv_x6p_kernel(ConvA
                 const int r = ml / TC, c = ml - r * TC, oh = oh0 + r, ow = ow0 + c;
                 if (oh < a.Ho && ow < a.Wo) {
                     const size_t o = ((size_t)(b * a.Ho + oh) * a.Wo + ow) * a.N + n;
-                    if (BF && a.ybf16 == 1 && a.splits == 1) ((uint16_t*)a.y)[o] = f2bf16(acc[i][e]);
+                    if (BF && a.ybf16 == 1 && a.splits == 1) ((uint16_t*)a.y)[o] = (uint16_t)f2bf(acc[i][e]);
                     else out[o] = acc[i][e];
                 }
             }
@@ -1459,45 +1338,11 @@ __global__ __launch_bounds__(512, (BMW == 64 ? 2 : 1)) void conv_x6_wgrad_kernel
         }
     };
     uint32_t pk[NP][4][2];   // plane, channel j, (k0k1, k2k3) packed bf16 pairs
-    auto split = [&](const VReg (&V)[4]) {
-        if constexpr (BF) {
-            // channel j of pixels (0, 1) and (2, 3): the low / high halves of dword j / 2
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint32_t sel = (j & 1) ? 0x07060302u : 0x05040100u;
-                const uint32_t d0 = (j < 2) ? V[0].x : V[0].y, d1 = (j < 2) ? V[1].x : V[1].y;
-                const uint32_t d2 = (j < 2) ? V[2].x : V[2].y, d3 = (j < 2) ? V[3].x : V[3].y;
-                pk[0][j][0] = __builtin_amdgcn_perm(d1, d0, sel);
-                pk[0][j][1] = __builtin_amdgcn_perm(d3, d2, sel);
-            }
-            return;
-        } else {
-        float c[3][4][4];   // plane, pixel i, channel j
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float x[4] = {V[i].x, V[i].y, V[i].z, V[i].w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float a0 = trunc16(x[j]), r1 = x[j] - a0, a1 = trunc16(r1);
-                c[0][i][j] = a0;
-                c[1][i][j] = a1;
-                c[2][i][j] = r1 - a1;
-            }
-        }
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                pk[pl][j][0] = hi16x2(c[pl][0][j], c[pl][1][j]);
-                pk[pl][j][1] = hi16x2(c[pl][2][j], c[pl][3][j]);
-            }
-        }
-    };
+    auto split = [&](const VReg (&V)[4]) { split4x4(V, pk); };
     auto store = [&](auto side_c, int buf) {
         constexpr int SIDE = decltype(side_c)::value;
         __bf16* L = lds[buf] + (SIDE ? NP * PA : 0);
         constexpr int P = SIDE ? PB : PA;
-        typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
         for (int pl = 0; pl < NP; ++pl)
 #pragma unroll
@@ -1534,19 +1379,7 @@ __global__ __launch_bounds__(512, (BMW == 64 ? 2 : 1)) void conv_x6_wgrad_kernel
 #pragma unroll
             for (int pl = 0; pl < NP; ++pl) fb[pl] = *(const bf16x8*)(L + NP * PA + pl * PB + eb);
 #pragma unroll
-            for (int i = 0; i < TM; ++i) {
-                if constexpr (BF) {
-                    acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[0], acc[i], 0, 0, 0);
-                    continue;
-                } else {
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][2], fb[0], acc[i], 0, 0, 0);
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][1], fb[1], acc[i], 0, 0, 0);
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[2], acc[i], 0, 0, 0);
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][1], fb[0], acc[i], 0, 0, 0);
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[1], acc[i], 0, 0, 0);
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[0], acc[i], 0, 0, 0);
-                }
-            }
+            for (int i = 0; i < TM; ++i) acc[i] = x6_mma32<NP>(fa[i], fb, acc[i]);
         }
     };
 
@@ -1711,28 +1544,12 @@ __global__ __launch_bounds__(512, 1) void conv_x6wws_kernel(ConvArgs a) {
     // split a 4-pixel x 4-channel micro-tile into 3 planes and store it transposed (per
     // plane and channel one 8-byte run of 4 consecutive k) — conv_x6_wgrad_kernel's split
     auto split_store = [&](const float4 (&V)[4], __bf16* L, int P) {
-        typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-        float c[3][4][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float x[4] = {V[i].x, V[i].y, V[i].z, V[i].w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float a0 = trunc16(x[j]), r1 = x[j] - a0, a1 = trunc16(r1);
-                c[0][i][j] = a0;
-                c[1][i][j] = a1;
-                c[2][i][j] = r1 - a1;
-            }
-        }
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                u32x2 q;
-                q.x = hi16x2(c[pl][0][j], c[pl][1][j]);
-                q.y = hi16x2(c[pl][2][j], c[pl][3][j]);
-                *(u32x2*)(L + pl * P + xidx2(row + j, 4 * kq)) = q;
-            }
+        split4x4_runs(V, [&](int pl, int j, uint32_t lo, uint32_t hi) {
+            u32x2 q;
+            q.x = lo;
+            q.y = hi;
+            *(u32x2*)(L + pl * P + xidx2(row + j, 4 * kq)) = q;
+        });
     };
     auto stage = [&](int buf, const float4 (&G)[4], const float4 (&X)[4]) {
         split_store(G, lds[buf], PA);
@@ -1772,15 +1589,7 @@ __global__ __launch_bounds__(512, 1) void conv_x6wws_kernel(ConvArgs a) {
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl) fa[pl] = *(const bf16x8*)(L + pl * PA + e);
 #pragma unroll
-                for (int jn = 0; jn < 2; ++jn) {
-                    // conv_x6_wgrad_kernel's order: x2y0, x1y1, x0y2, x1y0, x0y1, x0y0
-                    acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[2], fb[jn][0], acc[i][jn], 0, 0, 0);
-                    acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[jn][1], acc[i][jn], 0, 0, 0);
-                    acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[jn][2], acc[i][jn], 0, 0, 0);
-                    acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[jn][0], acc[i][jn], 0, 0, 0);
-                    acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[jn][1], acc[i][jn], 0, 0, 0);
-                    acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[jn][0], acc[i][jn], 0, 0, 0);
-                }
+                for (int jn = 0; jn < 2; ++jn) acc[i][jn] = x6_mma32<3>(fa, fb[jn], acc[i][jn]);
             }
         }
 #pragma unroll
@@ -1953,43 +1762,12 @@ __global__ __launch_bounds__(512, 1) void conv_x6wws256_kernel(ConvArgs a) {
         }
     };
     auto split_store = [&](const VReg (&V)[4], __bf16* L, int P, int r0) {
-        typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-        if constexpr (BF) {
-            // channel j of pixels (0, 1) and (2, 3): the low / high halves of dword j / 2
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint32_t sel = (j & 1) ? 0x07060302u : 0x05040100u;
-                const uint32_t d0 = (j < 2) ? V[0].x : V[0].y, d1 = (j < 2) ? V[1].x : V[1].y;
-                const uint32_t d2 = (j < 2) ? V[2].x : V[2].y, d3 = (j < 2) ? V[3].x : V[3].y;
-                u32x2 q;
-                q.x = __builtin_amdgcn_perm(d1, d0, sel);
-                q.y = __builtin_amdgcn_perm(d3, d2, sel);
-                *(u32x2*)(L + xidx2(r0 + j, 4 * kq)) = q;
-            }
-            return;
-        } else {
-        float c[3][4][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float x[4] = {V[i].x, V[i].y, V[i].z, V[i].w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float a0 = trunc16(x[j]), r1 = x[j] - a0, a1 = trunc16(r1);
-                c[0][i][j] = a0;
-                c[1][i][j] = a1;
-                c[2][i][j] = r1 - a1;
-            }
-        }
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                u32x2 q;
-                q.x = hi16x2(c[pl][0][j], c[pl][1][j]);
-                q.y = hi16x2(c[pl][2][j], c[pl][3][j]);
-                *(u32x2*)(L + pl * P + xidx2(r0 + j, 4 * kq)) = q;
-            }
-        }
+        split4x4_runs(V, [&](int pl, int j, uint32_t lo, uint32_t hi) {
+            u32x2 q;
+            q.x = lo;
+            q.y = hi;
+            *(u32x2*)(L + pl * P + xidx2(r0 + j, 4 * kq)) = q;
+        });
     };
     // step j = chunks KS j .. KS j + KS - 1 (zeros past the split's last chunk)
     auto load_step = [&](int j, VReg (&G)[KS][4], VReg (&X)[KS][2][4]) {
@@ -2034,19 +1812,7 @@ __global__ __launch_bounds__(512, 1) void conv_x6wws256_kernel(ConvArgs a) {
 #pragma unroll
                 for (int pl = 0; pl < NP; ++pl) fb[pl] = *(const bf16x8*)(L + NP * PA + pl * PB + eb);
 #pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    if constexpr (BF) {
-                        acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[0], acc[i][jn], 0, 0, 0);
-                        continue;
-                    } else {
-                    acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][2], fb[0], acc[i][jn], 0, 0, 0);
-                    acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][1], fb[1], acc[i][jn], 0, 0, 0);
-                    acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[2], acc[i][jn], 0, 0, 0);
-                    acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][1], fb[0], acc[i][jn], 0, 0, 0);
-                    acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[1], acc[i][jn], 0, 0, 0);
-                    acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[0], acc[i][jn], 0, 0, 0);
-                    }
-                }
+                for (int i = 0; i < 2; ++i) acc[i][jn] = x6_mma32<NP>(fa[i], fb, acc[i][jn]);
             }
         }
     };
@@ -2124,7 +1890,6 @@ __global__ __launch_bounds__(576, 1) void conv_x6pw_kernel(ConvArgs a) {
     const int m0 = mb * BMW, c0 = cb * XBK;
     const int t0 = ks * a.chunks_per_split;
     const int nchunks = min(a.chunks_per_split, a.nchunks - t0);
-    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
     // staging roles by wave (the x rows on waves 0-2, the gy tile on 3-4; measured 4 %
     // faster than keeping the three waves that share a SIMD, 0 / 4 / 8, free of staging)
@@ -2158,15 +1923,6 @@ __global__ __launch_bounds__(576, 1) void conv_x6pw_kernel(ConvArgs a) {
         if constexpr (BF) return bload8(r, ok ? elem * 2 : kBad);
         else return bload(r, ok ? elem * 4 : kBad);
     };
-    // channel j of pixels i and i + 1 as one bf16 pair (BF)
-    auto pair16 = [&](int j, int i) -> uint32_t {
-        if constexpr (BF) {
-            const uint32_t d0 = (j < 2) ? V[i].x : V[i].y, d1 = (j < 2) ? V[i + 1].x : V[i + 1].y;
-            return __builtin_amdgcn_perm(d1, d0, (j & 1) ? 0x07060302u : 0x05040100u);
-        } else {
-            return 0u;
-        }
-    };
     // loads of the loader's chunk (zeros past the split's last chunk: no branch)
     auto load_x = [&]() {
         const int ih = poh - a.pad + rr, iw0 = pseg * 32 - a.pad + 4 * g;
@@ -2185,80 +1941,56 @@ __global__ __launch_bounds__(576, 1) void conv_x6pw_kernel(ConvArgs a) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) V[i] = ld(gr, ok && ow0 + i < a.Wo, base + (ow0 + i) * a.Cg);
     };
+    // the x rows: per channel j the six pixels' five overlapping pairs (k, k + 1), stored
+    // as the three shifted copies (kw = 0, 1, 2) of 4 positions
     auto store_x = [&](__bf16* L) {
-        if constexpr (BF) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                uint32_t w[5];
-#pragma unroll
-                for (int k = 0; k < 5; ++k) w[k] = pair16(j, k);
-#pragma unroll
-                for (int kw = 0; kw < 3; ++kw) {
-                    u32x2 v;
-                    v.x = w[kw];
-                    v.y = w[kw + 2];
-                    *(u32x2*)(L + PA + (kw * 3 + rr) * PT + xidx2(4 * q + j, 4 * g)) = v;
-                }
-            }
-            return;
-        } else {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            float c[3][6];
+            float c[3][6];   // plane, pixel (the three-plane form)
+            if constexpr (!BF) {
 #pragma unroll
-            for (int i = 0; i < 6; ++i) {
-                const float x = j == 0 ? V[i].x : (j == 1 ? V[i].y : (j == 2 ? V[i].z : V[i].w));
-                const float a0 = trunc16(x), r1 = x - a0, a1 = trunc16(r1);
-                c[0][i] = a0;
-                c[1][i] = a1;
-                c[2][i] = r1 - a1;
+                for (int i = 0; i < 6; ++i) split3(chan(V[i], j), c[0][i], c[1][i], c[2][i]);
             }
 #pragma unroll
-            for (int pl = 0; pl < 3; ++pl) {
+            for (int pl = 0; pl < NP; ++pl) {
                 uint32_t w[5];
 #pragma unroll
-                for (int k = 0; k < 5; ++k) w[k] = hi16x2(c[pl][k], c[pl][k + 1]);
+                for (int k = 0; k < 5; ++k) {
+                    if constexpr (BF) w[k] = pair16(V[k], V[k + 1], j);
+                    else w[k] = hi16x2(c[pl][k], c[pl][k + 1]);
+                }
 #pragma unroll
                 for (int kw = 0; kw < 3; ++kw) {
                     u32x2 v;
                     v.x = w[kw];
                     v.y = w[kw + 2];
-                    *(u32x2*)(L + 3 * PA + ((kw * 3 + rr) * 3 + pl) * PT + xidx2(4 * q + j, 4 * g)) = v;
+                    *(u32x2*)(L + NP * PA + ((kw * 3 + rr) * NP + pl) * PT + xidx2(4 * q + j, 4 * g)) = v;
                 }
             }
-        }
         }
     };
+    // the gy micro-tile, channel by channel (md2::split4x4's arithmetic written out: its
+    // plane-major order measured 2.5 % slower here on the 512 -> 256 decoder layer)
     auto store_g = [&](__bf16* L) {
-        if constexpr (BF) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                u32x2 v;
-                v.x = pair16(j, 0);
-                v.y = pair16(j, 2);
-                *(u32x2*)(L + xidx2(4 * mq + j, 4 * kq)) = v;
-            }
-            return;
-        } else {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            float c[3][4];
+            float c[3][4];   // plane, pixel (the three-plane form)
+            if constexpr (!BF) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float x = j == 0 ? V[i].x : (j == 1 ? V[i].y : (j == 2 ? V[i].z : V[i].w));
-                const float a0 = trunc16(x), r1 = x - a0, a1 = trunc16(r1);
-                c[0][i] = a0;
-                c[1][i] = a1;
-                c[2][i] = r1 - a1;
+                for (int i = 0; i < 4; ++i) split3(chan(V[i], j), c[0][i], c[1][i], c[2][i]);
             }
 #pragma unroll
-            for (int pl = 0; pl < 3; ++pl) {
+            for (int pl = 0; pl < NP; ++pl) {
                 u32x2 v;
-                v.x = hi16x2(c[pl][0], c[pl][1]);
-                v.y = hi16x2(c[pl][2], c[pl][3]);
+                if constexpr (BF) {
+                    v.x = pair16(V[0], V[1], j);
+                    v.y = pair16(V[2], V[3], j);
+                } else {
+                    v.x = hi16x2(c[pl][0], c[pl][1]);
+                    v.y = hi16x2(c[pl][2], c[pl][3]);
+                }
                 *(u32x2*)(L + pl * PA + xidx2(4 * mq + j, 4 * kq)) = v;
             }
-        }
         }
     };
 
@@ -2285,17 +2017,7 @@ __global__ __launch_bounds__(576, 1) void conv_x6pw_kernel(ConvArgs a) {
                 const int e = xidx2(32 * i + lr, 16 * s + 8 * h);
 #pragma unroll
                 for (int pl = 0; pl < NP; ++pl) fa[pl] = *(const bf16x8*)(L + pl * PA + e);
-                if constexpr (BF) {
-                    acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[0], acc[i], 0, 0, 0);
-                    continue;
-                } else {
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[2], fb[0], acc[i], 0, 0, 0);
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[1], acc[i], 0, 0, 0);
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[2], acc[i], 0, 0, 0);
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[0], acc[i], 0, 0, 0);
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[1], acc[i], 0, 0, 0);
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[0], acc[i], 0, 0, 0);
-                }
+                acc[i] = x6_mma32<NP>(fa, fb, acc[i]);
             }
         }
     };
@@ -2398,8 +2120,7 @@ __global__ __launch_bounds__(256) void conv_reduce_kernel(const float4* part, fl
             s.w += v.w;
         }
         if constexpr (OM == 1) {
-            ((uint2*)y)[i] = make_uint2((uint32_t)f2bf16(s.x) | ((uint32_t)f2bf16(s.y) << 16),
-                                        (uint32_t)f2bf16(s.z) | ((uint32_t)f2bf16(s.w) << 16));
+            ((uint2*)y)[i] = make_uint2(f2bf(s.x) | (f2bf(s.y) << 16), f2bf(s.z) | (f2bf(s.w) << 16));
         } else if constexpr (OM == 2) {
             y[i] = make_float4(bf16_round(s.x), bf16_round(s.y), bf16_round(s.z), bf16_round(s.w));
         } else {
@@ -2456,8 +2177,7 @@ __global__ __launch_bounds__(256) void conv_reduce_scatter_kernel(const float4* 
                   ow = rem - oh * Wc;
         const size_t o = ((size_t)(b * oHf + 2 * oh + py) * oWf + 2 * ow + px) * N4 + q;
         if constexpr (OM == 1)
-            ((uint2*)y)[o] = make_uint2((uint32_t)f2bf16(s.x) | ((uint32_t)f2bf16(s.y) << 16),
-                                        (uint32_t)f2bf16(s.z) | ((uint32_t)f2bf16(s.w) << 16));
+            ((uint2*)y)[o] = make_uint2(f2bf(s.x) | (f2bf(s.y) << 16), f2bf(s.z) | (f2bf(s.w) << 16));
         else
             y[o] = s;
     }
@@ -2581,6 +2301,29 @@ double split_launch_cost() {
     return c;
 }
 
+// K split of an x6 GEMM by the wave-quantisation model: among smin .. smax splits the
+// count with the least rounds of `res` resident blocks (of `base` per split) x chunks
+// per block x round_cost (a chunk-round of 128 x 128 tiles ~1.5k cycles = 1), plus the
+// split reduction, which moves (splits + 1) M x N floats at ~2.4 KB/cycle chip-wide
+void split_k(ConvArgs& a, int base, int res, double round_cost, int smin, int smax) {
+    int best_s = 1;
+    double best_t = 1e30;
+    for (int sp = smin; sp <= smax; ++sp) {
+        const int per = (a.nchunks + sp - 1) / sp;
+        const int splits = (a.nchunks + per - 1) / per;
+        const int rounds = (base * splits + res - 1) / res;
+        const double red = splits > 1 ? (double)(splits + 1) * a.M * a.N * 4.0 / 2400.0 / 1536.0 + split_launch_cost()
+                                      : 0.0;
+        const double t = (double)rounds * per * round_cost + red;
+        if (t < best_t - 1e-9) {
+            best_t = t;
+            best_s = splits;
+        }
+    }
+    a.chunks_per_split = (a.nchunks + best_s - 1) / best_s;
+    a.splits = (a.nchunks + a.chunks_per_split - 1) / a.chunks_per_split;
+}
+
 // x6 plan: BN = 16 / 32 / 64 for N <= 16 / 32 / 64, else 128; BMX = 256 with MD2_CONV_BM256 (the caller's
 // autotune tries both); K split by the wave-quantisation model.  The weight-gradient
 // kernel is 128 wide, 64 or 128 rows (co) tall.
@@ -2592,30 +2335,13 @@ void plan_x6(ConvArgs& a, uint32_t flags, bool wgrad = false) {
     const int BMX = wgrad ? (a.M <= 64 ? 64 : 128) : ((BN == 128 && (flags & MD2_CONV_BM256)) ? 256 : 128);
     const int mblocks = (a.M + BMX - 1) / BMX, nblocks = (a.N + BN - 1) / BN;
     const int base = mblocks * nblocks, res = resident_blocks_x6(BN, BMX);
-    int best_s = 1;
-    double best_t = 1e30;
     const int smin = w256 ? (a.nchunks + 63) / 64 : 1;
     const int smax = std::max(smin, (flags & MD2_CONV_NO_SPLIT) ? 1 : (a.nchunks / 6 > 1 ? a.nchunks / 6 : 1));
-    for (int sp = smin; sp <= smax && sp <= std::max(64, smin); ++sp) {
-        const int per = (a.nchunks + sp - 1) / sp;
-        const int splits = (a.nchunks + per - 1) / per;
-        const int rounds = (base * splits + res - 1) / res;
-        // a chunk-round of blocks ~1.5k cycles (x BMX/128); the split reduction moves
-        // (splits + 1) M x N floats at ~2.4 KB/cycle chip-wide
-        const double red = splits > 1 ? (double)(splits + 1) * a.M * a.N * 4.0 / 2400.0 / 1536.0 + split_launch_cost()
-                                      : 0.0;
-        const double t = (double)rounds * per * (BMX / 128.0) * (BN / 128 > 1 ? BN / 128 : 1) + red;
-        if (t < best_t - 1e-9) {
-            best_t = t;
-            best_s = splits;
-        }
-    }
     a.bm = BMX;
     a.bn = BN;
     a.mblocks = mblocks;
     a.nblocks = nblocks;
-    a.chunks_per_split = (a.nchunks + best_s - 1) / best_s;
-    a.splits = (a.nchunks + a.chunks_per_split - 1) / a.chunks_per_split;
+    split_k(a, base, res, (BMX / 128.0) * (BN / 128 > 1 ? BN / 128 : 1), smin, std::min(smax, std::max(64, smin)));
 }
 
 template <int MODE>
@@ -2698,28 +2424,22 @@ void flat_k(ConvArgs& a, int mode) {
     }
 }
 
-void launch_bf(const ConvArgs& a, hipStream_t st) {
-    const dim3 grid(a.mblocks * a.nblocks * a.splits);
-    if (a.bm == 256) hipLaunchKernelGGL((conv_x6_kernel<128, 256, true>), grid, dim3(X6Geo<128, 256>::NT), 0, st, a);
-    else if (a.bn == 128)
-        hipLaunchKernelGGL((conv_x6_kernel<128, 128, true>), grid, dim3(X6Geo<128, 128>::NT), 0, st, a);
-    else if (a.bn == 64) hipLaunchKernelGGL((conv_x6_kernel<64, 128, true>), grid, dim3(X6Geo<64, 128>::NT), 0, st, a);
-    else if (a.bn == 32) hipLaunchKernelGGL((conv_x6_kernel<32, 128, true>), grid, dim3(X6Geo<32, 128>::NT), 0, st, a);
-    else hipLaunchKernelGGL((conv_x6_kernel<16, 128, true>), grid, dim3(X6Geo<16, 128>::NT), 0, st, a);
-}
-
+// the per-tap GEMM on three planes (BF = false; ws: MD2_CONV_WS) or on bf16 operands
+template <bool BF>
 void launch_x6(const ConvArgs& a, hipStream_t st, bool ws = false) {
     const dim3 grid(a.mblocks * a.nblocks * a.splits);
-    if (ws && a.bn == 128 && !a.flatk && !a.par) {   // warp-specialised (MD2_CONV_WS)
-        if (a.bm == 256) hipLaunchKernelGGL((conv_x6ws_kernel<256>), grid, dim3(512), 0, st, a);
-        else hipLaunchKernelGGL((conv_x6ws_kernel<128>), grid, dim3(512), 0, st, a);
-        return;
+    if constexpr (!BF) {
+        if (ws && a.bn == 128 && !a.flatk && !a.par) {   // warp-specialised
+            if (a.bm == 256) hipLaunchKernelGGL((conv_x6ws_kernel<256>), grid, dim3(512), 0, st, a);
+            else hipLaunchKernelGGL((conv_x6ws_kernel<128>), grid, dim3(512), 0, st, a);
+            return;
+        }
     }
-    if (a.bm == 256) hipLaunchKernelGGL((conv_x6_kernel<128, 256>), grid, dim3(X6Geo<128, 256>::NT), 0, st, a);
-    else if (a.bn == 128) hipLaunchKernelGGL((conv_x6_kernel<128, 128>), grid, dim3(X6Geo<128, 128>::NT), 0, st, a);
-    else if (a.bn == 64) hipLaunchKernelGGL((conv_x6_kernel<64, 128>), grid, dim3(X6Geo<64, 128>::NT), 0, st, a);
-    else if (a.bn == 32) hipLaunchKernelGGL((conv_x6_kernel<32, 128>), grid, dim3(X6Geo<32, 128>::NT), 0, st, a);
-    else hipLaunchKernelGGL((conv_x6_kernel<16, 128>), grid, dim3(X6Geo<16, 128>::NT), 0, st, a);
+    if (a.bm == 256) hipLaunchKernelGGL((conv_x6_kernel<128, 256, BF>), grid, dim3(X6Geo<128, 256>::NT), 0, st, a);
+    else if (a.bn == 128) hipLaunchKernelGGL((conv_x6_kernel<128, 128, BF>), grid, dim3(X6Geo<128, 128>::NT), 0, st, a);
+    else if (a.bn == 64) hipLaunchKernelGGL((conv_x6_kernel<64, 128, BF>), grid, dim3(X6Geo<64, 128>::NT), 0, st, a);
+    else if (a.bn == 32) hipLaunchKernelGGL((conv_x6_kernel<32, 128, BF>), grid, dim3(X6Geo<32, 128>::NT), 0, st, a);
+    else hipLaunchKernelGGL((conv_x6_kernel<16, 128, BF>), grid, dim3(X6Geo<16, 128>::NT), 0, st, a);
 }
 
 // Patch kernel (MD2_CONV_X6 | MD2_CONV_PATCH): 3x3 stride-1 forward / input gradient with
@@ -2752,27 +2472,12 @@ void plan_x6p(ConvArgs& a, uint32_t flags) {
     a.nchunks = a.C / XBK;
     const int mblocks = a.B * a.ptr * a.ptc, nblocks = (a.N + BN - 1) / BN;
     const int base = mblocks * nblocks, res = BN == 128 ? 256 : 512;   // blocks per CU: 1 (BN 128) / 2
-    int best_s = 1;
-    double best_t = 1e30;
     const int smax = (flags & MD2_CONV_NO_SPLIT) ? 1 : a.nchunks;
-    for (int sp = 1; sp <= smax && sp <= 64; ++sp) {
-        const int per = (a.nchunks + sp - 1) / sp;
-        const int splits = (a.nchunks + per - 1) / per;
-        const int rounds = (base * splits + res - 1) / res;
-        const double red = splits > 1 ? (double)(splits + 1) * a.M * a.N * 4.0 / 2400.0 / 1536.0 + split_launch_cost()
-                                      : 0.0;
-        const double t = (double)rounds * per * 9.0 * (BMX / 128.0) + red;
-        if (t < best_t - 1e-9) {
-            best_t = t;
-            best_s = splits;
-        }
-    }
     a.bm = BMX;
     a.bn = BN;
     a.mblocks = mblocks;
     a.nblocks = nblocks;
-    a.chunks_per_split = (a.nchunks + best_s - 1) / best_s;
-    a.splits = (a.nchunks + a.chunks_per_split - 1) / a.chunks_per_split;
+    split_k(a, base, res, 9.0 * (BMX / 128.0), 1, std::min(smax, 64));   // a chunk here is nine taps
     a.flatk = best_tc;   // carried to launch_x6p (the kernel itself does not read flatk)
 }
 
@@ -2895,8 +2600,8 @@ int run_dgrad_s2(const md2_conv_desc* d, const float* gy, const float* w, float*
     __bf16* planes = (bf || (d->flags & MD2_CONV_PRESPLIT)) ? (__bf16*)w : (__bf16*)ws;
     const size_t part_off = bf ? 0 : x6_planes_bytes(d);
     auto go = [&](const ConvArgs& a) {
-        if (bf) launch_bf(a, st);
-        else launch_x6(a, st);
+        if (bf) launch_x6<true>(a, st);
+        else launch_x6<false>(a, st);
     };
     if (!bf && !(d->flags & MD2_CONV_PRESPLIT)) {
         const int nw = d->out_channels * d->kernel_h * d->kernel_w * d->in_channels;
@@ -3058,7 +2763,7 @@ int run_bf(const md2_conv_desc* d, int mode, const void* A, const void* B, void*
     } else if (patch) {
         launch_x6p<true>(a, st);
     } else {
-        launch_bf(a, st);
+        launch_x6<true>(a, st);
     }
     if (a.splits > 1) launch_reduce((const float4*)a.y, (float4*)out, a.M * a.N / 4, a.splits, st, a.ybf16);
     const hipError_t e = hipGetLastError();
@@ -3107,7 +2812,7 @@ int run(const md2_conv_desc* d, int mode, const float* A, const float* B, float*
             hipLaunchKernelGGL(conv_wsplit_kernel, dim3((nw + 255) / 256), dim3(256), 0, st, B, planes,
                                d->out_channels, d->kernel_h * d->kernel_w, d->in_channels, mode == MODE_DGRAD ? 1 : 0);
         if (patch) launch_x6p(a, st);
-        else launch_x6(a, st, (d->flags & MD2_CONV_WS) != 0);
+        else launch_x6<false>(a, st, (d->flags & MD2_CONV_WS) != 0);
     } else if (mode == MODE_FWD) launch<MODE_FWD>(a, BN, st);
     else if (mode == MODE_DGRAD) launch<MODE_DGRAD>(a, BN, st);
     else launch<MODE_WGRAD>(a, BN, st);

@@ -26,11 +26,14 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "md2_x6.h"
 #include "md2hot.h"
 
 int md2_report_error(int code, const char* msg);
 
 namespace {
+
+using namespace md2;   // md2_x6.h: the split-bf16 format, md2_bf16.h: f2bf / bf16_round
 
 constexpr int kThreads = 256;
 
@@ -133,7 +136,7 @@ __global__ __launch_bounds__(kThreads) void conv3_direct_lds_kernel(const float*
 // Split-bf16 MFMA form (MD2_CONV_X6 in the descriptor's flags): the same correlation as
 // a GEMM with M = output pixels, N = COUT, K = 9 taps x CIN (k = tap·CIN + ci, padded to
 // whole 32-k steps with zero weights), on v_mfma_f32_16x16x32_bf16 with six products of
-// three exact bf16 planes per operand (f32-class, conv.hip's x6 scheme).  The GEMM is 16
+// three exact bf16 planes per operand (f32-class, the x6 scheme of md2_x6.h).  The GEMM is 16
 // or 32 columns wide, so the weights — KS steps x NB column blocks x 3 planes of one
 // fragment per lane, 60-120 VGPRs — live in registers for the block's whole life; a
 // block walks output tiles (4 rows x 64 columns) persistently: it stages the tile's
@@ -143,24 +146,6 @@ __global__ __launch_bounds__(kThreads) void conv3_direct_lds_kernel(const float*
 // channels of one tap at the pixel's window position) and 6 x NB MFMAs.  Every input
 // element is split once per tile instead of once per tap.
 constexpr int kXR = 4, kXC = 64;
-
-__device__ __forceinline__ float x6_trunc16(float x) {
-    return __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, x) & 0xFFFF0000u);
-}
-__device__ __forceinline__ uint32_t x6_hi16x2(float lo, float hi) {
-    return __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, hi), __builtin_bit_cast(uint32_t, lo), 0x07060302u);
-}
-// fp32 -> bf16 bits / the bf16 value as fp32, round to nearest even (torch's cast)
-__device__ __forceinline__ uint16_t x6_f2bf(float v) {
-    const uint32_t u = __builtin_bit_cast(uint32_t, v);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
-    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-__device__ __forceinline__ float x6_rne(float v) { return __builtin_bit_cast(float, (uint32_t)x6_f2bf(v) << 16); }
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // BF (MD2_CONV_BF16, config C5): x bf16, the tap-major fp32 weights rounded to bf16 (as
 // autocast casts them) into one plane, one MFMA per fragment pair, y written as bf16 (RNE)
@@ -188,17 +173,14 @@ __global__ __launch_bounds__(kThreads, 2) void conv3_x6_kernel(const float* __re
             for (int j = 0; j < 8; ++j) {
                 const int k = 32 * s + 8 * g + j;
                 float v = k < 9 * CIN ? wk[k * COUT + 16 * nb + col] : 0.f;
-                if constexpr (BF) v = x6_rne(v);
-                const float a0 = x6_trunc16(v), r1 = v - a0, a1 = x6_trunc16(r1);
-                c[0][j] = a0;
-                c[1][j] = a1;
-                c[2][j] = r1 - a1;
+                if constexpr (BF) v = bf16_round(v);
+                split3(v, c[0][j], c[1][j], c[2][j]);
             }
 #pragma unroll
             for (int pl = 0; pl < NPL; ++pl)
                 wf[s][nb][pl] = __builtin_bit_cast(
-                    bf16x8, u32x4{x6_hi16x2(c[pl][0], c[pl][1]), x6_hi16x2(c[pl][2], c[pl][3]),
-                                  x6_hi16x2(c[pl][4], c[pl][5]), x6_hi16x2(c[pl][6], c[pl][7])});
+                    bf16x8, u32x4{hi16x2(c[pl][0], c[pl][1]), hi16x2(c[pl][2], c[pl][3]),
+                                  hi16x2(c[pl][4], c[pl][5]), hi16x2(c[pl][6], c[pl][7])});
         }
     const int ntiles = B * tiles_r * tiles_c;
     // the tile's patch is loaded into registers one tile ahead (issued before the current
@@ -236,15 +218,10 @@ __global__ __launch_bounds__(kThreads, 2) void conv3_x6_kernel(const float* __re
                 const float e[4] = {v.x, v.y, v.z, v.w};
                 float c[3][4];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float a0 = x6_trunc16(e[j]), r1 = e[j] - a0, a1 = x6_trunc16(r1);
-                    c[0][j] = a0;
-                    c[1][j] = a1;
-                    c[2][j] = r1 - a1;
-                }
+                for (int j = 0; j < 4; ++j) split3(e[j], c[0][j], c[1][j], c[2][j]);
 #pragma unroll
                 for (int pl = 0; pl < NPL; ++pl)
-                    patch[pl][i] = u32x2{x6_hi16x2(c[pl][0], c[pl][1]), x6_hi16x2(c[pl][2], c[pl][3])};
+                    patch[pl][i] = u32x2{hi16x2(c[pl][0], c[pl][1]), hi16x2(c[pl][2], c[pl][3])};
             }
         }
         __syncthreads();
@@ -267,23 +244,12 @@ __global__ __launch_bounds__(kThreads, 2) void conv3_x6_kernel(const float* __re
                 const int e = ((wid + kh) * PC + 16 * m + col + kw) * CIN + ci0;
                 bf16x8 fa[NPL];
                 fa[0] = *(const bf16x8*)(P0 + e);
-                if constexpr (BF) {
-#pragma unroll
-                    for (int nb = 0; nb < NB; ++nb)
-                        acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], wf[s][nb][0], acc[nb], 0, 0, 0);
-                } else {
+                if constexpr (!BF) {
                     fa[1] = *(const bf16x8*)(P1 + e);
                     fa[2] = *(const bf16x8*)(P2 + e);
-#pragma unroll
-                    for (int nb = 0; nb < NB; ++nb) {
-                        acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[2], wf[s][nb][0], acc[nb], 0, 0, 0);
-                        acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[1], wf[s][nb][1], acc[nb], 0, 0, 0);
-                        acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], wf[s][nb][2], acc[nb], 0, 0, 0);
-                        acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[1], wf[s][nb][0], acc[nb], 0, 0, 0);
-                        acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], wf[s][nb][1], acc[nb], 0, 0, 0);
-                        acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], wf[s][nb][0], acc[nb], 0, 0, 0);
-                    }
                 }
+#pragma unroll
+                for (int nb = 0; nb < NB; ++nb) acc[nb] = x6_mma16<NPL>(fa, wf[s][nb], acc[nb]);
             }
             // D[row = 4 g + i][col]: pixel ow0 + 16 m + 4 g + i, channel 16 nb + col
             if (oh < Ho) {
@@ -294,7 +260,7 @@ __global__ __launch_bounds__(kThreads, 2) void conv3_x6_kernel(const float* __re
                         const size_t o = ((size_t)(b * Ho + oh) * Wo + ow) * COUT + col;
 #pragma unroll
                         for (int nb = 0; nb < NB; ++nb) {
-                            if constexpr (BF) ((uint16_t*)y)[o + 16 * nb] = x6_f2bf(acc[nb][i]);
+                            if constexpr (BF) ((uint16_t*)y)[o + 16 * nb] = (uint16_t)f2bf(acc[nb][i]);
                             else y[o + 16 * nb] = acc[nb][i];
                         }
                     }
@@ -324,7 +290,6 @@ __device__ __forceinline__ int wg_off(int pix, int q4) {   // bf16 offset of cha
     if constexpr (C == 16) return ((pix ^ (((pix >> 3) & 1) << 2)) * 16) + 4 * q4;
     else return pix * 32 + 4 * (q4 ^ (((pix >> 3) & 1) << 2));
 }
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ s16x4 tr_read(const __bf16* p) {
     return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p);
 }
@@ -357,15 +322,10 @@ __global__ __launch_bounds__(kThreads, 2) void conv3_x6_wgrad_kernel(const float
         const float e[4] = {v.x, v.y, v.z, v.w};
         float c[3][4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float a0 = x6_trunc16(e[j]), r1 = e[j] - a0, a1 = x6_trunc16(r1);
-            c[0][j] = a0;
-            c[1][j] = a1;
-            c[2][j] = r1 - a1;
-        }
+        for (int j = 0; j < 4; ++j) split3(e[j], c[0][j], c[1][j], c[2][j]);
 #pragma unroll
         for (int pl = 0; pl < NPL; ++pl)
-            *(u32x2*)(base + pl * stride + off) = u32x2{x6_hi16x2(c[pl][0], c[pl][1]), x6_hi16x2(c[pl][2], c[pl][3])};
+            *(u32x2*)(base + pl * stride + off) = u32x2{hi16x2(c[pl][0], c[pl][1]), hi16x2(c[pl][2], c[pl][3])};
     };
     auto put_bf = [&](__bf16* base, int off, uint2 u) { *(u32x2*)(base + off) = u32x2{u.x, u.y}; };
     const int ntiles = B * tiles_r * tiles_c;
@@ -444,17 +404,7 @@ __global__ __launch_bounds__(kThreads, 2) void conv3_x6_wgrad_kernel(const float
                                     hi = tr_read(&xs[pl][wg_off<CIN>(xp + 4, 4 * cb + p4)]);
                         fb[pl] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
                     }
-                    if constexpr (BF) {
-                        acc[tap][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], fb[0], acc[tap][cb], 0, 0, 0);
-                    } else {
-                        f32x4 c = acc[tap][cb];
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[2], fb[0], c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[1], fb[1], c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], fb[2], c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[1], fb[0], c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], fb[1], c, 0, 0, 0);
-                        acc[tap][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], fb[0], c, 0, 0, 0);
-                    }
+                    acc[tap][cb] = x6_mma16<NPL>(fa, fb, acc[tap][cb]);
                 }
             }
         }

@@ -17,6 +17,8 @@ __device__ __forceinline__ uint32_t f2bf(float f) {
     if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;   // NaN stays NaN
     return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
 }
+// fp32 rounded to a bf16 value
+__device__ __forceinline__ float bf16_round(float f) { return bf2f(f2bf(f)); }
 
 template <typename T>
 __device__ __forceinline__ float4 ld4T(const void* p, size_t off) {

@@ -38,6 +38,7 @@
 
 #include "md2hot.h"
 #include "md2_bf16.h"
+#include "md2_x6.h"
 
 namespace {
 
@@ -86,15 +87,7 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
-// Workgroups are dealt round-robin over the 8 XCDs (MI355X_MICROARCH.md, dispatch
-// placement; speed only, never correctness).  Give every XCD a contiguous range of
-// logical blocks so its private L2 streams a contiguous slice of the images instead
-// of all XCDs fetching every image.  Bijective for any n.
-__device__ __forceinline__ int xcd_contiguous_block(int bid, int n) {
-    const int q = n >> 3, r = n & 7;
-    const int xcd = bid & 7, idx = bid >> 3;
-    return xcd < r ? xcd * (q + 1) + idx : r * (q + 1) + (xcd - r) * q + idx;
-}
+using md2::xcd_contiguous_block;   // md2_x6.h: every XCD a contiguous range of logical blocks
 
 // Loads at a uniform base + a non-negative 32-bit element index: the byte offset is
 // formed in 32 bits, so the compiler emits the SGPR-base + VGPR-offset form of

@@ -1,7 +1,7 @@
 // stem.hip — weight gradient of the ResNet stem convolution (conv1: 7x7, stride 2,
 // padding 3, C -> 64, no bias; networks/resnet_encoder.py -> torchvision conv1) on
 // split-bf16 MFMA (f32-class: three exact bf16 planes per operand, six products,
-// f32 accumulation — the scheme of conv.hip's x6 kernels).
+// f32 accumulation — the x6 scheme defined in md2_x6.h).
 //
 // The stem's input is data (the normalised frames), so its backward is the weight
 // gradient alone: dW[co][ky][kx][ci] = Σ_p dy[p][co] · x[p's 7x7 window][ky][kx][ci]
@@ -41,16 +41,14 @@
 #include <stdlib.h>
 
 #include "md2_bn_expr.h"
+#include "md2_x6.h"
 #include "md2hot.h"
 
 int md2_report_error(int code, const char* msg);
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+using namespace md2;   // md2_x6.h: the split-bf16 format, md2_bf16.h: f2bf / bf16_round
 
 constexpr int kCo = 64;
 constexpr int kWaves = 7;               // one per kernel row
@@ -64,9 +62,8 @@ constexpr int kCG = 3;                  // channels per group (one frame)
 // 39: 2.6x fewer conflict cycles in an exhaustive model of the build and the store)
 constexpr int kRP = 39;
 constexpr int kRaw = 7 * kCG * 2 * kRP;  // floats per staged chunk ([kh][ci][parity][kRP])
-constexpr int kXBK = 32;
-constexpr int kPA = kCo * kXBK;         // bf16 per dy plane (64 co x 32 pixels)
-constexpr int kPT = 32 * kXBK;          // bf16 per B tile plane (32 rows x 32 pixels)
+constexpr int kPA = kCo * XBK;         // bf16 per dy plane (64 co x 32 pixels)
+constexpr int kPT = 32 * XBK;          // bf16 per B tile plane (32 rows x 32 pixels)
 constexpr int kOut = 49 * kCG;          // outputs per output channel per group
 constexpr int kBlocksPerCU = 2;
 constexpr int kMaxChunks = 64;          // chunks per K split at most
@@ -87,34 +84,6 @@ struct StemArgs {
     const float* coef;                  // [3][bn_groups][64]: bn_bwd_final's k1, k2, k3
     int bn_groups, bn_ipg;              // BatchNorm groups, images per group
 };
-
-// Exact three-way split by truncation (conv.hip): x == x0 + x1 + x2, each a bf16
-__device__ __forceinline__ float trunc16(float x) {
-    return __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, x) & 0xFFFF0000u);
-}
-__device__ __forceinline__ uint32_t hi16x2(float lo, float hi) {
-    return __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, hi), __builtin_bit_cast(uint32_t, lo), 0x07060302u);
-}
-// fp32 -> bf16 bits / the bf16 value as fp32, round to nearest even (torch's cast)
-__device__ __forceinline__ uint16_t f2bf16(float v) {
-    const uint32_t u = __builtin_bit_cast(uint32_t, v);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
-    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-__device__ __forceinline__ float bf16_rne(float v) { return __builtin_bit_cast(float, (uint32_t)f2bf16(v) << 16); }
-// [rows][32 k] bf16 planes with 16-byte quads XOR-swizzled by (row >> 2) & 3 and rows
-// r, r ^ 1 swapped in odd row quads (conv.hip xidx2): conflict-free fragment reads
-// and conflict-free 8-byte stores from lanes covering two adjacent rows
-__device__ __forceinline__ int xidx2(int r, int k) {
-    r ^= (r >> 2) & 1;
-    return r * kXBK + ((((k >> 3) ^ (r >> 2)) & 3) << 3) + (k & 7);
-}
-__device__ __forceinline__ int xcd_contiguous_block(int bid, int n) {   // conv.hip
-    const int q = n >> 3, r = n & 7;
-    const int xcd = bid & 7, idx = bid >> 3;
-    return xcd < r ? xcd * (q + 1) + idx : r * (q + 1) + (xcd - r) * q + idx;
-}
-__device__ __forceinline__ void lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // two 7-wave blocks per CU put four waves on two of the SIMDs: <= 128 VGPRs
 template <int C>
@@ -223,13 +192,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
         for (int j = 0; j < 4; ++j) {
             float c[3][4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float x = j == 0 ? GV[i].x : (j == 1 ? GV[i].y : (j == 2 ? GV[i].z : GV[i].w));
-                const float a0 = trunc16(x), r1 = x - a0, a1 = trunc16(r1);
-                c[0][i] = a0;
-                c[1][i] = a1;
-                c[2][i] = r1 - a1;
-            }
+            for (int i = 0; i < 4; ++i) split3(chan(GV[i], j), c[0][i], c[1][i], c[2][i]);
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl) {
                 u32x2 v;
@@ -255,12 +218,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
             for (int i = 0; i < 4; ++i) v[i] = src[((kh * kCG + ci) * 2 + (kx & 1)) * kRP + 4 * g + i + (kx >> 1)];
             float c[3][4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float a0 = trunc16(v[i]), r1 = v[i] - a0, a1 = trunc16(r1);
-                c[0][i] = a0;
-                c[1][i] = a1;
-                c[2][i] = r1 - a1;
-            }
+            for (int i = 0; i < 4; ++i) split3(v[i], c[0][i], c[1][i], c[2][i]);
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl) {
                 u32x2 q;
@@ -282,7 +240,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
     auto mma = [&]() {
         const __bf16* LB = Bt + wid * 3 * kPT;
 #pragma unroll
-        for (int s = 0; s < kXBK / 16; ++s) {
+        for (int s = 0; s < XBK / 16; ++s) {
             bf16x8 fb[3];
             const int eb = xidx2(lr, 16 * s + 8 * h);
 #pragma unroll
@@ -293,12 +251,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
                 const int e = xidx2(32 * i + lr, 16 * s + 8 * h);
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl) fa[pl] = *(const bf16x8*)(At + pl * kPA + e);
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[2], fb[0], acc[i], 0, 0, 0);
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[1], acc[i], 0, 0, 0);
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[2], acc[i], 0, 0, 0);
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[0], acc[i], 0, 0, 0);
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[1], acc[i], 0, 0, 0);
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[0], acc[i], 0, 0, 0);
+                acc[i] = x6_mma32<3>(fa, fb, acc[i]);
             }
         }
     };
@@ -368,13 +321,11 @@ __device__ __forceinline__ int tr_goff(int px, int co4) {   // dy: 4 pixels of o
     const int sw = ((px >> 1) & 1) | (((px >> 3) & 1) << 1);
     return px * kCo + 4 * (co4 ^ (sw << 2));
 }
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ bf16x8 tr_pair(const __bf16* lo, const __bf16* hi) {
     const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)lo);
     const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)hi);
     return __builtin_bit_cast(bf16x8, __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
 }
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // FUSE: dy is not in memory — the BatchNorm backward's apply pass is folded into the dy
 // fetch: dy = k1·(g' - k2 - (z - mean)·k3) with g' = g gated by the ReLU mask, per channel
@@ -444,19 +395,7 @@ __global__ __launch_bounds__(kTThreads, 2) void stem_x6_wgrad_tr_kernel(StemArgs
 #pragma unroll
                 for (int pl = 0; pl < NPL; ++pl) fa[pl] = tr_pair(&gs[pl][glo], &gs[pl][ghi]);
 #pragma unroll
-                for (int ni = 0; ni < NB; ++ni) {
-                    if constexpr (BF) {
-                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], fb[ni][0], acc[mi][ni], 0, 0, 0);
-                        continue;
-                    }
-                    f32x4 c = acc[mi][ni];
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[2], fb[ni][0], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[1], fb[ni][1], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], fb[ni][2], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[1], fb[ni][0], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], fb[ni][1], c, 0, 0, 0);
-                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], fb[ni][0], c, 0, 0, 0);
-                }
+                for (int ni = 0; ni < NB; ++ni) acc[mi][ni] = x6_mma16<NPL>(fa, fb[ni], acc[mi][ni]);
             }
         }
     };
@@ -478,12 +417,7 @@ __global__ __launch_bounds__(kTThreads, 2) void stem_x6_wgrad_tr_kernel(StemArgs
             const float e[4] = {v.x, v.y, v.z, v.w};
             float c[3][4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float a0 = trunc16(e[j]), r1 = e[j] - a0, a1 = trunc16(r1);
-                c[0][j] = a0;
-                c[1][j] = a1;
-                c[2][j] = r1 - a1;
-            }
+            for (int j = 0; j < 4; ++j) split3(e[j], c[0][j], c[1][j], c[2][j]);
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl)
                 *(u32x2*)(base + pl * stride + o) = u32x2{hi16x2(c[pl][0], c[pl][1]), hi16x2(c[pl][2], c[pl][3])};
@@ -646,12 +580,7 @@ __global__ __launch_bounds__(kTThreads, 2) void stem_x6_wgrad_tr_kernel(StemArgs
             const float e[4] = {v.x, v.y, v.z, v.w};
             float c[3][4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float a0 = trunc16(e[j]), r1 = e[j] - a0, a1 = trunc16(r1);
-                c[0][j] = a0;
-                c[1][j] = a1;
-                c[2][j] = r1 - a1;
-            }
+            for (int j = 0; j < 4; ++j) split3(e[j], c[0][j], c[1][j], c[2][j]);
             const int o = tr_goff(px, co4);
 #pragma unroll
             for (int pl = 0; pl < NPL; ++pl) *(u32x2*)&gs[pl][o] = u32x2{hi16x2(c[pl][0], c[pl][1]), hi16x2(c[pl][2], c[pl][3])};
@@ -764,19 +693,7 @@ __global__ __launch_bounds__(kTThreads, 2) void stem_x6_wgrad_tr_kernel(StemArgs
 #pragma unroll
                 for (int pl = 0; pl < NPL; ++pl) fa[pl] = tr_pair(&gs[pl][glo], &gs[pl][ghi]);
 #pragma unroll
-                for (int ni = 0; ni < NB; ++ni) {
-                    if constexpr (BF) {
-                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], fb[ni][0], acc[mi][ni], 0, 0, 0);
-                        continue;
-                    }
-                    f32x4 c = acc[mi][ni];
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[2], fb[ni][0], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[1], fb[ni][1], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], fb[ni][2], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[1], fb[ni][0], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], fb[ni][1], c, 0, 0, 0);
-                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], fb[ni][0], c, 0, 0, 0);
-                }
+                for (int ni = 0; ni < NB; ++ni) acc[mi][ni] = x6_mma16<NPL>(fa, fb[ni], acc[mi][ni]);
             }
         }
         __syncthreads();   // restaged next chunk
@@ -832,7 +749,7 @@ __global__ __launch_bounds__(256) void stem_wgrad_final_kernel(StemArgs a) {
 // lanes of one pixel group read overlapping windows, the overlap served by L1.  K is
 // padded to KP = 16·⌈7C/16⌉ with zero weights (C = 3: 21 -> 32, C = 6: 42 -> 48).
 // The fragments are split into bf16 planes in registers (exact truncation split, six
-// products: f32-class, conv.hip's x6 scheme); the weights, split once per block into
+// products: f32-class, the x6 scheme of md2_x6.h); the weights, split once per block into
 // their fragment image in LDS (84 KB at C = 3, 126 KB at C = 6), are read conflict-free
 // as 1-KB runs.  A wave owns 64 pixels of one output row x all 64 channels (2 x 2
 // 32x32 accumulators) and walks its tiles persistently; the next step's fragments are
@@ -939,11 +856,11 @@ __device__ __forceinline__ void stem_fwd_tile(const StemFwdArgs& a, const u32x4*
             const uint32_t (&cur)[2][4] = rb[q % (kPD + 1)];
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                const bf16x8 fb = __builtin_bit_cast(bf16x8, wf[(q * 2 + j) * 64 + lane]);
+                const bf16x8 fb[1] = {__builtin_bit_cast(bf16x8, wf[(q * 2 + j) * 64 + lane])};
 #pragma unroll
                 for (int p = 0; p < 2; ++p) {
-                    const bf16x8 fa = __builtin_bit_cast(bf16x8, u32x4{cur[p][0], cur[p][1], cur[p][2], cur[p][3]});
-                    acc[p][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb, acc[p][j], 0, 0, 0);
+                    const bf16x8 fa[1] = {__builtin_bit_cast(bf16x8, u32x4{cur[p][0], cur[p][1], cur[p][2], cur[p][3]})};
+                    acc[p][j] = x6_mma32<1>(fa, fb, acc[p][j]);
                 }
             }
         }
@@ -955,7 +872,7 @@ __device__ __forceinline__ void stem_fwd_tile(const StemFwdArgs& a, const u32x4*
                 const int ow = ow0 + 32 * p + (e & 3) + 8 * (e >> 2) + 4 * h;
                 if (!EDGE || ow < a.Wo) {
 #pragma unroll
-                    for (int j = 0; j < 2; ++j) yrow[(size_t)ow * kCo + 32 * j + lr] = f2bf16(acc[p][j][e]);
+                    for (int j = 0; j < 2; ++j) yrow[(size_t)ow * kCo + 32 * j + lr] = (uint16_t)f2bf(acc[p][j][e]);
                 }
             }
         return;
@@ -990,14 +907,7 @@ __device__ __forceinline__ void stem_fwd_tile(const StemFwdArgs& a, const u32x4*
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl) fb[pl] = __builtin_bit_cast(bf16x8, wf[((q * 2 + j) * 3 + pl) * 64 + lane]);
 #pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                acc[p][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[p][2], fb[0], acc[p][j], 0, 0, 0);
-                acc[p][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[p][1], fb[1], acc[p][j], 0, 0, 0);
-                acc[p][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[p][0], fb[2], acc[p][j], 0, 0, 0);
-                acc[p][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[p][1], fb[0], acc[p][j], 0, 0, 0);
-                acc[p][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[p][0], fb[1], acc[p][j], 0, 0, 0);
-                acc[p][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[p][0], fb[0], acc[p][j], 0, 0, 0);
-            }
+            for (int p = 0; p < 2; ++p) acc[p][j] = x6_mma32<3>(fa[p], fb, acc[p][j]);
         }
     }
     // D row (pixel) = 32 p + (e & 3) + 8 (e >> 2) + 4 h, column (channel) = 32 j + lr
@@ -1034,11 +944,8 @@ __global__ __launch_bounds__(64 * kFwdWaves, 1) void stem_x6_fwd_kernel(StemFwdA
             float v = 0.f;
             if (k < 7 * C)
                 v = a.w_cl ? a.w[((co * 7 + kh) * 7 + kw) * C + ci] : a.w[((co * C + ci) * 7 + kh) * 7 + kw];
-            if constexpr (BF) v = bf16_rne(v);   // autocast's cast of the weight: plane 0 alone
-            const float a0 = trunc16(v), r1 = v - a0, a1 = trunc16(r1);
-            c[0][i] = a0;
-            c[1][i] = a1;
-            c[2][i] = r1 - a1;
+            if constexpr (BF) v = bf16_round(v);   // autocast's cast of the weight: plane 0 alone
+            split3(v, c[0][i], c[1][i], c[2][i]);
         }
 #pragma unroll
         for (int pl = 0; pl < NPL; ++pl)
