@@ -919,6 +919,53 @@ int md2_stem_wgrad_bn(const md2_stem_desc* desc, const float* x, const float* gr
                       const uint8_t* relu_mask, const float* save_mean, const float* coef, int bn_groups,
                       float* grad_weight, void* workspace, void* stream);
 
+/*
+ * 16-bit depth maps for the KITTI depth-prediction benchmark (csrc/eval.hip): the
+ * reference's export loop, evaluate_depth.py:148-163 — cv2.resize of the scaled disparity
+ * to 1216 x 352, depth = 5.4 / disp, clip to [0, 80], uint16(depth * 256), per image on the
+ * host — for a batch in one launch on `stream`.  New symbols under ABI 24, no version bump
+ * (as md2_disp_colorize).
+ *
+ * disp (B,1,in_height,in_width): the network's sigmoid output; disp_flipped: the same for
+ * the horizontally flipped images (MD2_DEPTH16_POST_PROCESS; else may be NULL); out:
+ * uint16 (B,out_height,out_width) contiguous, 2-byte aligned, written completely.  Per
+ * output pixel, with md2_depth_eval's own device functions:
+ *   - the four neighbours' scaled disparities, fp32 product then fp32 sum (disp_to_depth
+ *     with min_depth / max_depth; 1 and INFINITY make it the identity), blended in fp64
+ *     with batch_post_process_disparity's masks when asked;
+ *   - r = the half-pixel bilinear weights of md2_depth_eval applied in fp64, with
+ *     in_height / out_height and in_width / out_width;
+ *   - v = scale_factor / r, v = min(max(v, 0), clip_max); out = (uint16)(v * quant),
+ *     truncated toward zero.
+ * Where the reference leaves the result to numpy's undefined float-to-integer casts this
+ * build defines it: r == +0 gives clip_max * quant, r < 0 (and -0) gives 0, NaN gives 0.
+ * No workspace, no atomics: bitwise repeatable, hipGraph-capturable.
+ * Refused (MD2_ERR_ARG): NULL desc, disp or out (or disp_flipped with the flag), a
+ * non-positive size, batch > 65535, batch * in_height * in_width or batch * out_height *
+ * out_width at or above 2^31, unknown flag bits, a non-zero reserved field, min_depth /
+ * max_depth not 0 < min < max, a scale_factor, clip_max or quant that is not positive and
+ * finite, clip_max * quant > 65535, an odd `out` address.
+ */
+#define MD2_DEPTH16_POST_PROCESS (1u << 0)
+
+typedef struct md2_depth16_desc {
+    int32_t batch;                  /* B images, 1..65535 */
+    int32_t in_height, in_width;    /* of disp */
+    int32_t out_height, out_width;  /* of out; the benchmark's maps are 352 x 1216 */
+    uint32_t flags;                 /* MD2_DEPTH16_* */
+    double min_depth, max_depth;    /* of disp_to_depth, Python doubles as in md2_eval_desc; offset 24 */
+    double scale_factor;            /* the reference's STEREO_SCALE_FACTOR, 5.4 (offset 40) */
+    double clip_max;                /* MAX_DEPTH, 80 */
+    double quant;                   /* counts per metre, 256 */
+    int64_t reserved;               /* 0; the struct is 72 bytes */
+} md2_depth16_desc;
+
+/* MD2_OK, or MD2_ERR_ARG (and md2_last_error) for a desc md2_depth_export16 would refuse:
+ * the op has no workspace query to ask, and a caller sizes `out` from the desc */
+int md2_depth_export16_check(const md2_depth16_desc* desc);
+int md2_depth_export16(const md2_depth16_desc* desc, const float* disp, const float* disp_flipped, uint16_t* out,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

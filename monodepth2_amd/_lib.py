@@ -76,7 +76,8 @@ EXPORTS = ["md2_abi_version", "md2_last_error", "md2_workspace_bytes", "md2_sele
            "md2_disp_colorize", "md2_disp_colorize_workspace_bytes",
            "md2_bn_pool_fwd_supported", "md2_bn_pool_fwd", "md2_bn_bwd_reduce_mask", "md2_bn_coef_offset",
            "md2_stem_wgrad_bn_supported", "md2_stem_wgrad_bn",
-           "md2_aug_plan_create_mixed", "md2_aug_run_mixed"]
+           "md2_aug_plan_create_mixed", "md2_aug_run_mixed",
+           "md2_depth_export16", "md2_depth_export16_check"]
 
 DTYPE_F32 = 0    # md2_desc.disp_dtype
 DTYPE_BF16 = 1
@@ -216,7 +217,22 @@ class VizDesc(ctypes.Structure):
                 ("flags", ctypes.c_uint32), ("reserved", ctypes.c_int32)]
 
 
+# md2_depth_export16 (csrc/eval.hip): a new symbol under ABI 24, no version bump
+DEPTH16_POST_PROCESS = 1 << 0
+
+
+class Depth16Desc(ctypes.Structure):
+    _fields_ = [("batch", ctypes.c_int32), ("in_height", ctypes.c_int32), ("in_width", ctypes.c_int32),
+                ("out_height", ctypes.c_int32), ("out_width", ctypes.c_int32), ("flags", ctypes.c_uint32),
+                ("min_depth", ctypes.c_double), ("max_depth", ctypes.c_double), ("scale_factor", ctypes.c_double),
+                ("clip_max", ctypes.c_double), ("quant", ctypes.c_double), ("reserved", ctypes.c_int64)]
+
+
 def _declare(L):
+    L.md2_depth_export16.restype = ctypes.c_int
+    L.md2_depth_export16.argtypes = [ctypes.POINTER(Depth16Desc)] + [_vp] * 4
+    L.md2_depth_export16_check.restype = ctypes.c_int
+    L.md2_depth_export16_check.argtypes = [ctypes.POINTER(Depth16Desc)]
     # the stem's fused BatchNorm passes: new symbols under ABI 24, no version bump
     L.md2_bn_pool_fwd_supported.restype = ctypes.c_int
     L.md2_bn_pool_fwd_supported.argtypes = [ctypes.POINTER(BnDesc), ctypes.c_int, ctypes.c_int]

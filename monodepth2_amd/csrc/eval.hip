@@ -30,6 +30,9 @@
 // median convention picks from them at the end.  Histograms and counts are integer
 // atomics (they commute); no float atomic anywhere, so results are bitwise repeatable.
 // Without MD2_EVAL_MEDIAN_SCALE the chain is predict, reduce, finalise.
+//
+// md2_depth_export16 (further down) is the `benchmark` split's 16-bit depth export on the
+// same prediction: one launch, no workspace.
 
 #include <hip/hip_runtime.h>
 
@@ -350,6 +353,85 @@ __global__ __launch_bounds__(64) void eval_final_kernel(EvalArgs a) {
     }
 }
 
+// md2_depth_export16: the `benchmark` split's export (evaluate_depth.py:148-163: cv2.resize
+// of the scaled disparity to 1216 x 352, scale_factor / disp, clip, uint16(depth * 256)) for
+// a batch, one launch.  grid (blocks, B); a thread owns kExportPixels adjacent pixels of one
+// output row, formed as eval_predict_kernel forms its prediction (the same device functions,
+// fp64 after disp_to_depth) and stored as one 8-byte word where the address allows, else as
+// 4-byte words between 2-byte ends: rows of an odd width, or images at an odd offset, start
+// on any 2-byte boundary.  The input is a few KB per image and stays in L2; the 2 bytes per
+// pixel written are the traffic.
+// This build's choice where the reference leaves the result to numpy's undefined casts: a
+// resized disparity of 0 gives clip * quant (-0 and any negative one give 0), NaN gives 0.
+constexpr int kExportPixels = 4;
+constexpr int kMaxExportBlocks = 1024;   // per image; the rest is a grid stride
+
+template <bool PP>
+__global__ __launch_bounds__(kThreads) void export16_kernel(EvalArgs a, uint16_t* out, double clip, double quant) {
+    const int b = blockIdx.y;
+    const size_t dbase = (size_t)b * a.h * a.w;
+    uint16_t* img = out + (size_t)b * a.npix;
+    const int groups = (a.GW - 1) / kExportPixels + 1;
+    const long long total = (long long)a.GH * groups;
+    for (long long g = (long long)blockIdx.x * kThreads + threadIdx.x; g < total; g += (long long)gridDim.x * kThreads) {
+        const int oy = (int)(g / groups), ox0 = (int)(g - (long long)oy * groups) * kExportPixels;
+        const int n = a.GW - ox0 < kExportPixels ? a.GW - ox0 : kExportPixels;
+        int ya, yb;
+        double fy;
+        lerp_coord(oy, a.sy, a.h, ya, yb, fy);
+        unsigned q[kExportPixels];
+#pragma unroll
+        for (int i = 0; i < kExportPixels; ++i) {
+            q[i] = 0;
+            if (i < n) {
+                int xa, xb;
+                double fx;
+                lerp_coord(ox0 + i, a.sx, a.w, xa, xb, fx);
+                const double v00 = scaled_disp<PP>(a, dbase, ya, xa), v01 = scaled_disp<PP>(a, dbase, ya, xb);
+                const double v10 = scaled_disp<PP>(a, dbase, yb, xa), v11 = scaled_disp<PP>(a, dbase, yb, xb);
+                const double r = (1.0 - fy) * ((1.0 - fx) * v00 + fx * v01) + fy * ((1.0 - fx) * v10 + fx * v11);
+                double v = a.sf / r;
+                v = v > 0.0 ? (v < clip ? v : clip) : 0.0;   // NaN fails the first comparison
+                q[i] = (unsigned)(v * quant);                 // <= clip * quant <= 65535
+            }
+        }
+        uint16_t* p = img + (size_t)oy * a.GW + ox0;
+        const uintptr_t addr = reinterpret_cast<uintptr_t>(p);
+        if (n == kExportPixels && (addr & 7) == 0) {
+            *reinterpret_cast<uint2*>(p) = make_uint2(q[0] | (q[1] << 16), q[2] | (q[3] << 16));
+        } else if (addr & 2) {   // one pixel up to the 4-byte boundary, a word, what is left
+            p[0] = (uint16_t)q[0];
+            if (n >= 3) *reinterpret_cast<unsigned*>(p + 1) = q[1] | (q[2] << 16);
+            if (n == 2) p[1] = (uint16_t)q[1];
+            if (n == 4) p[3] = (uint16_t)q[3];
+        } else {
+            if (n >= 2) *reinterpret_cast<unsigned*>(p) = q[0] | (q[1] << 16);
+            if (n == 1) p[0] = (uint16_t)q[0];
+            if (n == 4) *reinterpret_cast<unsigned*>(p + 2) = q[2] | (q[3] << 16);
+            if (n == 3) p[2] = (uint16_t)q[2];
+        }
+    }
+}
+
+const char* check_export(const md2_depth16_desc* d) {
+    if (!d) return "depth_export16: NULL desc";
+    if (d->batch < 1 || d->in_height < 1 || d->in_width < 1 || d->out_height < 1 || d->out_width < 1)
+        return "depth_export16: batch, in_height, in_width, out_height, out_width must be positive";
+    if (d->batch > kMaxBatch) return "depth_export16: batch too large (at most 65535 images per call)";
+    const long long in = (long long)d->in_height * d->in_width, on = (long long)d->out_height * d->out_width;
+    if (in >= (1ll << 31) || on >= (1ll << 31) || d->batch * in >= (1ll << 31) || d->batch * on >= (1ll << 31))
+        return "depth_export16: batch too large (2^31 pixels)";
+    if (d->flags & ~MD2_DEPTH16_POST_PROCESS) return "depth_export16: unknown flags";
+    if (d->reserved != 0) return "depth_export16: reserved must be 0";
+    if (!(d->min_depth > 0.0) || !(d->max_depth > d->min_depth)) return "depth_export16: need 0 < min_depth < max_depth";
+    const double inf = (double)INFINITY;
+    if (!(d->scale_factor > 0.0) || !(d->scale_factor < inf) || !(d->clip_max > 0.0) || !(d->clip_max < inf) ||
+        !(d->quant > 0.0) || !(d->quant < inf))
+        return "depth_export16: scale_factor, clip_max and quant must be positive and finite";
+    if (d->clip_max * d->quant > 65535.0) return "depth_export16: clip_max * quant above 65535 (the output holds 16 bits)";
+    return nullptr;
+}
+
 size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 struct Layout {
@@ -451,6 +533,39 @@ int md2_depth_eval(const md2_eval_desc* d, const float* disp, const float* disp_
     }
     hipLaunchKernelGGL(eval_reduce_kernel, grid, block, 0, st, a);
     hipLaunchKernelGGL(eval_final_kernel, dim3(l.P), dim3(64), 0, st, a);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? MD2_OK : md2_report_error(MD2_ERR_HIP, hipGetErrorString(e));
+}
+
+int md2_depth_export16_check(const md2_depth16_desc* d) {
+    if (const char* msg = check_export(d)) return md2_report_error(MD2_ERR_ARG, msg);
+    return MD2_OK;
+}
+
+int md2_depth_export16(const md2_depth16_desc* d, const float* disp, const float* disp_flipped, uint16_t* out,
+                       void* stream) {
+    if (const char* msg = check_export(d)) return md2_report_error(MD2_ERR_ARG, msg);
+    if (!disp || !out) return md2_report_error(MD2_ERR_ARG, "depth_export16: NULL operand");
+    const bool pp = d->flags & MD2_DEPTH16_POST_PROCESS;
+    if (pp && !disp_flipped)
+        return md2_report_error(MD2_ERR_ARG, "depth_export16: MD2_DEPTH16_POST_PROCESS needs disp_flipped");
+    if (reinterpret_cast<uintptr_t>(out) & 1) return md2_report_error(MD2_ERR_ARG, "depth_export16: out must be 2-byte aligned");
+    EvalArgs a = {};
+    a.disp = disp;
+    a.dispf = disp_flipped;
+    a.B = d->batch; a.h = d->in_height; a.w = d->in_width; a.GH = d->out_height; a.GW = d->out_width;
+    a.npix = d->out_height * d->out_width;
+    const double lo = 1.0 / d->max_depth, hi = 1.0 / d->min_depth;   // as md2_depth_eval
+    a.lo = (float)lo;
+    a.range = (float)(hi - lo);
+    a.sf = d->scale_factor;
+    a.sy = (double)d->in_height / (double)d->out_height;
+    a.sx = (double)d->in_width / (double)d->out_width;
+    const long long groups = (long long)d->out_height * ((d->out_width - 1) / kExportPixels + 1);
+    const long long want = (groups + kThreads - 1) / kThreads;
+    const dim3 grid((unsigned)(want > kMaxExportBlocks ? kMaxExportBlocks : want), d->batch), block(kThreads);
+    hipLaunchKernelGGL(pp ? export16_kernel<true> : export16_kernel<false>, grid, block, 0, (hipStream_t)stream, a, out,
+                       d->clip_max, d->quant);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? MD2_OK : md2_report_error(MD2_ERR_HIP, hipGetErrorString(e));
 }

@@ -18,6 +18,10 @@ Two formulations of the reference are selectable:
 The resize is half-pixel bilinear (F.interpolate(align_corners=False)); cv2.resize of the
 reference's evaluate_depth.py is the same formula, bit parity with it is not measured.
 There is no CPU path: a CPU tensor is an error.
+
+`benchmark_depth_maps(disp, ...)` is the `benchmark` split's export on the same prediction
+(ABI `md2_depth_export16`, one launch): 16-bit maps of depth * 256 at 352 x 1216;
+`write_benchmark_pngs` writes them as the reference's numbered PNGs.
 """
 from __future__ import annotations
 
@@ -129,3 +133,89 @@ def depth_metrics(disp: torch.Tensor, gt: torch.Tensor, *, mode: str = "evaluate
         return out
     keys = ws[:4 * B * GH * GW].view(torch.int32).view(B, GH, GW)
     return out, keys.view(torch.float32), keys != -1
+
+
+def depth16_desc(batch: int, in_hw: Sequence[int], out_hw: Sequence[int] = (352, 1216), *, post_process: bool = False,
+                 scale_factor: float = 5.4, clip_max: float = 80.0, quant: float = 256.0, min_depth: float = 0.1,
+                 max_depth: float = 100.0) -> _lib.Depth16Desc:
+    return _lib.Depth16Desc(batch, in_hw[0], in_hw[1], out_hw[0], out_hw[1],
+                            _lib.DEPTH16_POST_PROCESS if post_process else 0, min_depth, max_depth, scale_factor,
+                            clip_max, quant, 0)
+
+
+def check_depth16(d: _lib.Depth16Desc):
+    """Raises RuntimeError with the library's message for a desc md2_depth_export16 refuses."""
+    _lib.check(_lib.lib().md2_depth_export16_check(ctypes.byref(d)), "md2_depth_export16_check")
+
+
+def benchmark_depth_maps(disp: torch.Tensor, post_process_disp: Optional[torch.Tensor] = None,
+                         out_hw: Sequence[int] = (352, 1216), scale_factor: float = 5.4, clip_max: float = 80.0,
+                         quant: float = 256.0, min_depth: float = 0.1, max_depth: float = 100.0,
+                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The KITTI benchmark's 16-bit depth maps of `disp` (B,1,h,w) or (B,h,w), the raw
+    sigmoid output, in one launch (csrc/eval.hip, `md2_depth_export16`): the export loop of
+    evaluate_depth.py:148-163.  Per output pixel: disp_to_depth's scaled disparity,
+    post-processed with `post_process_disp` (the output for the flipped images, not flipped
+    back) if given, resized to `out_hw` with half-pixel bilinear weights in fp64, then
+    (uint16)(min(max(scale_factor / r, 0), clip_max) * quant), truncated.  r == 0 gives
+    clip_max * quant, a negative r gives 0, NaN gives 0 (this build's choice: the reference
+    leaves them to numpy's undefined casts).
+
+    Returns (B, OH, OW) on the device in torch.int16 storage that holds the uint16 bit
+    patterns (a depth above 127.996 m at 256 counts per metre reads negative as int16);
+    `.cpu().numpy().view(np.uint16)` is the image.  `out`: a (B, OH, OW) contiguous int16
+    tensor on disp's device to write into (it may be a view at any 2-byte offset).
+    Disparities that already went through disp_to_depth: min_depth=1, max_depth=inf.
+    GPU only; the input checks are depth_metrics'.
+    """
+    if not torch.is_tensor(disp) or not disp.is_cuda:
+        raise RuntimeError("benchmark_depth_maps is GPU only (HIP kernels, no CPU fallback)")
+    if disp.dim() == 3:
+        disp = disp.unsqueeze(1)
+    if disp.dim() != 4 or disp.shape[1] != 1:
+        raise ValueError(f"expected disp (B,1,h,w) or (B,h,w), got {tuple(disp.shape)}")
+    if disp.dtype != torch.float32:
+        raise ValueError("benchmark_depth_maps supports float32")
+    disp = disp.detach().contiguous()
+    flipped = None
+    if post_process_disp is not None:
+        flipped = post_process_disp.detach()
+        if flipped.dim() == 3:
+            flipped = flipped.unsqueeze(1)
+        if flipped.shape != disp.shape or flipped.dtype != torch.float32 or flipped.device != disp.device:
+            raise ValueError("post_process_disp must match disp in shape, dtype and device")
+        flipped = flipped.contiguous()
+    B, _, h, w = disp.shape
+    OH, OW = int(out_hw[0]), int(out_hw[1])
+    d = depth16_desc(B, (h, w), (OH, OW), post_process=flipped is not None, scale_factor=scale_factor,
+                     clip_max=clip_max, quant=quant, min_depth=min_depth, max_depth=max_depth)
+    check_depth16(d)   # before `out` is sized from it
+    if out is None:
+        out = torch.empty((B, OH, OW), dtype=torch.int16, device=disp.device)
+    elif (not torch.is_tensor(out) or out.dtype != torch.int16 or tuple(out.shape) != (B, OH, OW)
+          or out.device != disp.device or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous int16 tensor of shape {(B, OH, OW)} on {disp.device}")
+    _lib.check(_lib.lib().md2_depth_export16(ctypes.byref(d), disp.data_ptr(),
+                                             flipped.data_ptr() if flipped is not None else None, out.data_ptr(),
+                                             _lib.stream(disp.device)), "md2_depth_export16")
+    return out
+
+
+def write_benchmark_pngs(maps, save_dir: str, start: int = 0):
+    """`maps` (N, OH, OW), benchmark_depth_maps' int16 tensor or a uint16 / int16 array, as
+    the files `{:010d}.png` of `save_dir`, numbered from `start`: 16-bit greyscale PNGs
+    (Pillow mode I;16), what evaluate_depth.py:161-162 writes through cv2.  Returns the paths."""
+    import os
+
+    from PIL import Image
+    arr = maps.cpu().numpy() if torch.is_tensor(maps) else np.asarray(maps)
+    if arr.ndim != 3 or arr.dtype not in (np.int16, np.uint16):
+        raise ValueError(f"maps must be (N, OH, OW) int16 or uint16, got {arr.shape} {arr.dtype}")
+    arr = np.ascontiguousarray(arr).view(np.uint16)
+    os.makedirs(save_dir, exist_ok=True)
+    paths = []
+    for i, a in enumerate(arr):
+        path = os.path.join(save_dir, "{:010d}.png".format(start + i))
+        Image.fromarray(a).save(path)   # a uint16 array is mode I;16
+        paths.append(path)
+    return paths

@@ -12,12 +12,21 @@ copy at the end.
 
 Ground truth: --gt_poses, a KITTI `poses/NN.txt` (default <data_path>/poses/NN.txt).
 Predictions: --ext_poses_to_eval, the (N,4,4) float32 `poses.npy` this command and the
-reference write, or `predict_poses` on images the caller loaded, with the checkpoint in
---load_weights_folder (pose_encoder.pth, pose.pth).
+reference write; or the checkpoint in --load_weights_folder (pose_encoder.pth, pose.pth)
+run by `predict_poses` on images the caller loaded; or, as in the reference, that
+checkpoint run on the frames test_files_09.txt / test_files_10.txt name under --data_path
+(--split_dir, default splits/odom/ beside this package; the lists are not shipped):
+datasets.KITTIOdomDataset decodes frames k and k + 1 of every line, loader.BatchLoader
+(list order, --batch_size lines per pass, the partial last batch included) resizes them to
+--height x --width on the device, bit-equal to the reference's PIL pipeline.
 
-Out of scope here, refused with a clear error: loading the odometry frames from
---data_path (this tree decodes no JPEGs and ships no splits/odom lists), and the `posecnn`
-and `shared` pose models, which the reference's evaluate_pose supports neither.
+    python -m monodepth2_amd.evaluate_pose --eval_split odom_9 --load_weights_folder W \\
+        --data_path KITTI_ODOM --split_dir splits/odom
+
+Out of scope: shipping the split lists (a missing one is an `options.SplitListMissing`, a
+FileNotFoundError that names --split_dir and, as the refusal of this route was before it
+existed, a NotImplementedError), and the `posecnn` and `shared` pose models, which the
+reference's evaluate_pose supports neither.
 """
 from __future__ import annotations
 
@@ -28,11 +37,13 @@ import numpy as np
 import torch
 
 from . import networks
-from .options import MonodepthOptions
+from .datasets import readlines
+from .options import MonodepthOptions, SplitListMissing
 from .pose_eval_ops import trajectory_ate
 from .pose_ops import poses_to_transforms
 
 TRACK_LENGTH = 5   # evaluate_pose.py:118
+SPLITS_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "splits")
 
 
 def load_gt_poses(path: str) -> np.ndarray:
@@ -42,6 +53,32 @@ def load_gt_poses(path: str) -> np.ndarray:
     if rows.shape[1] != 12:
         raise ValueError("{}: expected 12 numbers per line, found {}".format(path, rows.shape[1]))
     return rows.reshape(-1, 3, 4)
+
+
+def _pose_batch(pose_encoder, pose_decoder, first: torch.Tensor, second: torch.Tensor) -> torch.Tensor:
+    """One pass of evaluate_pose.py:94-100 on n frame pairs (n,3,H,W) each: (n,4,4).  The
+    caller holds eval mode and no_grad."""
+    pair = [first.contiguous(), second.contiguous()]
+    axisangle, translation = pose_decoder([pose_encoder([pair])])
+    aa, tr = axisangle[:, 0, 0].float().unsqueeze(0), translation[:, 0, 0].float().unsqueeze(0)
+    return poses_to_transforms(aa, tr, [False])[0]
+
+
+def _predict_pairs(pose_encoder, pose_decoder, pairs) -> torch.Tensor:
+    """`_pose_batch` over an iterable of (first, second) frame batches, in eval mode under
+    no_grad; the modules' training flags are restored."""
+    was = pose_encoder.training, pose_decoder.training
+    pose_encoder.eval()
+    pose_decoder.eval()
+    out = []
+    try:
+        with torch.no_grad():
+            for first, second in pairs:
+                out.append(_pose_batch(pose_encoder, pose_decoder, first, second))
+    finally:
+        pose_encoder.train(was[0])
+        pose_decoder.train(was[1])
+    return torch.cat(out)
 
 
 def predict_poses(pose_encoder, pose_decoder, images: torch.Tensor, batch_size: int = 16) -> torch.Tensor:
@@ -54,22 +91,46 @@ def predict_poses(pose_encoder, pose_decoder, images: torch.Tensor, batch_size: 
     on their own; nothing is forced.  The modules' training flags are restored."""
     if images.dim() != 4 or images.shape[1] != 3 or images.shape[0] < 2:
         raise ValueError(f"images must be (M, 3, H, W) with M >= 2, got {tuple(images.shape)}")
-    was = pose_encoder.training, pose_decoder.training
-    pose_encoder.eval()
-    pose_decoder.eval()
-    out = []
+    last = images.shape[0] - 1
+
+    def pairs():
+        for i in range(0, last, batch_size):
+            n = min(batch_size, last - i)
+            yield images[i:i + n], images[i + 1:i + 1 + n]
+
+    return _predict_pairs(pose_encoder, pose_decoder, pairs())
+
+
+def split_lines(opt, sequence_id: int):
+    """The lines of test_files_NN.txt in --split_dir (default splits/odom/ beside this
+    package, where the reference keeps them; the lists are not shipped)."""
+    folder = getattr(opt, "split_dir", None) or os.path.join(SPLITS_DIR, "odom")
+    path = os.path.join(folder, "test_files_{:02d}.txt".format(sequence_id))
+    if not os.path.isfile(path):
+        raise SplitListMissing(
+            "no split list at {}: evaluating the frames under --data_path needs it, and the split lists are not "
+            "shipped with this package (shipping them is out of scope); pass --split_dir DIR with "
+            "DIR/test_files_09.txt and DIR/test_files_10.txt (the reference's splits/odom/ folder)".format(path))
+    return readlines(path)
+
+
+def predict_from_disk(pose_encoder, pose_decoder, opt, lines, device) -> torch.Tensor:
+    """evaluate_pose.py:60-102 from --data_path: every line's frames k and k + 1, decoded by
+    datasets.KITTIOdomDataset and resized to --height x --width on the device
+    (loader.BatchLoader in list order, --batch_size lines per pass, the partial last batch
+    included; scale 0 only), then the per-batch body of `predict_poses`.  The reference
+    feeds `color_aug`, which is `color` when is_train is False."""
+    from .datasets import KITTIOdomDataset
+    from .loader import BatchLoader
+    dataset = KITTIOdomDataset(opt.data_path, lines, opt.height, opt.width, [0, 1], 1, is_train=False,
+                               img_ext=".png" if opt.png else ".jpg")
+    loader = BatchLoader(dataset, opt.batch_size, shuffle=False, drop_last=False, num_workers=opt.num_workers,
+                         device=device)
     try:
-        with torch.no_grad():
-            for i in range(0, images.shape[0] - 1, batch_size):
-                n = min(batch_size, images.shape[0] - 1 - i)
-                pair = [images[i:i + n].contiguous(), images[i + 1:i + 1 + n].contiguous()]
-                axisangle, translation = pose_decoder([pose_encoder([pair])])
-                aa, tr = axisangle[:, 0, 0].float().unsqueeze(0), translation[:, 0, 0].float().unsqueeze(0)
-                out.append(poses_to_transforms(aa, tr, [False])[0])
+        return _predict_pairs(pose_encoder, pose_decoder,
+                              ((batch[("color_aug", 0, 0)], batch[("color_aug", 1, 0)]) for batch in loader))
     finally:
-        pose_encoder.train(was[0])
-        pose_decoder.train(was[1])
-    return torch.cat(out)
+        loader.close()
 
 
 def evaluate_poses(pred_poses, gt_global_poses, track_length: int = TRACK_LENGTH, device=None) -> Dict[str, object]:
@@ -112,15 +173,14 @@ def load_networks(folder: str, num_layers: int, device):
 
 def evaluate(opt, images: torch.Tensor = None):
     """evaluate_pose.py:49-129.  Predictions come from --ext_poses_to_eval (poses.npy), or
-    from `images` (M,3,H,W), the frames of the sequence in order, and the checkpoint in
-    --load_weights_folder; then poses.npy is saved there, as the reference does."""
+    from the checkpoint in --load_weights_folder run on `images` (M,3,H,W), the frames of
+    the sequence in order, or, without them, on the frames test_files_NN.txt names under
+    --data_path (`predict_from_disk`); then poses.npy is saved there, as the reference does."""
     if opt.eval_split not in ("odom_9", "odom_10"):
         raise SystemExit("eval_split should be either odom_9 or odom_10")
     sequence_id = int(opt.eval_split.split("_")[1])
     ext = getattr(opt, "ext_poses_to_eval", None)
-    if ext is None and images is None:
-        raise NotImplementedError("loading KITTI odometry frames from --data_path is out of scope (no dataset "
-                                  "readers in this tree): pass --ext_poses_to_eval, or call evaluate(opt, images)")
+    lines = split_lines(opt, sequence_id) if ext is None and images is None else None
     gt_path = getattr(opt, "gt_poses", None) or os.path.join(opt.data_path, "poses", "{:02d}.txt".format(sequence_id))
     if not os.path.isfile(gt_path):
         raise SystemExit("Cannot find ground-truth poses at {} (set --gt_poses)".format(gt_path))
@@ -138,7 +198,10 @@ def evaluate(opt, images: torch.Tensor = None):
         print("-> Loading weights from {}".format(folder))
         pose_encoder, pose_decoder = load_networks(folder, opt.num_layers, device)
         print("-> Computing pose predictions")
-        pred = predict_poses(pose_encoder, pose_decoder, images.to(device))
+        if images is not None:
+            pred = predict_poses(pose_encoder, pose_decoder, images.to(device))
+        else:
+            pred = predict_from_disk(pose_encoder, pose_decoder, opt, lines, device)
         save_path = os.path.join(folder, "poses.npy")
     res = evaluate_poses(pred, load_gt_poses(gt_path), TRACK_LENGTH, device)
     print(format_results(res))

@@ -8,7 +8,9 @@ pin_memory=True, drop_last=True)` (trainer.py:127-139) around a dataset whose
 (augment.GpuAugmentMixed), so a batch is:
 
   1. the epoch's permutation (drawn from `seed` and the epoch), cut into batches with the
-     last partial one dropped, batches dealt to ranks as `rank::world_size`;
+     last partial one dropped, batches dealt to ranks as `rank::world_size` (with
+     `drop_last=False`, the evaluators' order, the partial batch is produced too: one
+     process only, and a second GPU plan of the tail's size, since a plan's batch is fixed);
   2. every image file of the batch opened (sizes are known from the headers), frame
      offsets laid out 256-byte aligned in one ragged buffer;
   3. the frames decoded by up to min(num_workers, 16) THREADS (PIL releases the GIL while
@@ -61,9 +63,14 @@ class _Staged:
 
 class BatchLoader:
     def __init__(self, dataset, batch_size: int, shuffle: bool = True, seed: int = 0, num_workers: int = 0,
-                 rank: int = 0, world_size: int = 1, device=None, with_depth: bool = False, prefetch: int = 2):
+                 rank: int = 0, world_size: int = 1, device=None, with_depth: bool = False, prefetch: int = 2,
+                 drop_last: bool = True):
         if not (0 <= rank < world_size):
             raise ValueError(f"rank {rank} outside world size {world_size}")
+        if not drop_last and world_size > 1:
+            raise ValueError("drop_last=False is the evaluation order, one process: it cannot be dealt to "
+                             f"world_size {world_size} ranks in equal steps")
+        self.drop_last = bool(drop_last)
         self.dataset = dataset
         self.batch_size = batch_size
         self.shuffle = shuffle
@@ -82,6 +89,7 @@ class BatchLoader:
         self.frame_ids = list(dataset.frame_idxs)
         self.aug = GpuAugmentMixed(dataset.height, dataset.width, self.frame_ids, batch_size, dataset.num_scales,
                                    device=self.device)
+        self._tail_aug: Optional[GpuAugmentMixed] = None   # drop_last=False: the partial batch's plan
         # ring: one slot being filled, `prefetch` queued, IN_FLIGHT whose upload may be running
         self._ring = self.prefetch + 1 + IN_FLIGHT
         self._pinned: List[Optional[torch.Tensor]] = [None] * self._ring
@@ -100,11 +108,25 @@ class BatchLoader:
             random.Random(item_seed(self.seed, epoch, -1)).shuffle(order)
         B = self.batch_size
         full = [order[i * B:(i + 1) * B] for i in range(len(order) // B)]   # drop_last
+        if not self.drop_last:                                              # one rank: every item, the tail too
+            return full + ([order[len(full) * B:]] if len(order) % B else [])
         per_rank = len(full) // self.world_size                             # equal steps on every rank
         return full[self.rank::self.world_size][:per_rank]
 
     def __len__(self):
+        if not self.drop_last:
+            return -(-len(self.dataset) // self.batch_size)
         return (len(self.dataset) // self.batch_size) // self.world_size
+
+    def _aug_for(self, n: int) -> GpuAugmentMixed:
+        """The plan of a batch of `n` items: a plan's batch size is fixed, so the partial
+        last batch of drop_last=False gets one of its own, built when it is first met."""
+        if n == self.batch_size:
+            return self.aug
+        if self._tail_aug is None or self._tail_aug.batch_size != n:
+            self._tail_aug = GpuAugmentMixed(self.dataset.height, self.dataset.width, self.frame_ids, n,
+                                             self.dataset.num_scales, device=self.device)
+        return self._tail_aug
 
     # ---------------------------------------------------------------- staging
     def _map(self, fn, seq):
@@ -173,7 +195,7 @@ class BatchLoader:
             self._uploaded[st.slot].record()
             draws = [it.draw for it in st.items]
             sides = [it.side for it in st.items] if "s" in self.frame_ids else None
-            inputs = self.aug(dev, [it.size for it in st.items], st.offsets, draws, sides)
+            inputs = self._aug_for(len(st.items))(dev, [it.size for it in st.items], st.offsets, draws, sides)
             if self.with_depth:
                 inputs["depth_gt"] = self.dataset.get_depths(st.items, device=self.device).unsqueeze(1)
         return inputs

@@ -75,8 +75,13 @@ _FLAGS = [
     ("--gt_poses", dict(type=str, help="build: KITTI poses file (12 numbers per line) for evaluate_pose; default "
                                        "<data_path>/poses/NN.txt")),
     ("--ext_poses_to_eval", dict(type=str, help="build: external poses.npy (N,4,4) float32 for evaluate_pose")),
-    ("--split_dir", dict(type=str, help="build: folder holding train_files.txt and val_files.txt for train; "
-                                        "default splits/<split>/ beside the package (the lists are not shipped)")),
+    ("--split_dir", dict(type=str, help="build: folder holding train_files.txt and val_files.txt for train, "
+                                        "test_files.txt for evaluate_depth, test_files_09.txt / test_files_10.txt "
+                                        "for evaluate_pose; default splits/<split>/ beside the package (the lists "
+                                        "are not shipped)")),
+    ("--eigen_to_benchmark_ids", dict(type=str, help="build: the reference's eigen_to_benchmark_ids.npy for "
+                                                     "--eval_eigen_to_benchmark; default splits/benchmark/"
+                                                     "eigen_to_benchmark_ids.npy beside the package")),
     ("--seed", dict(type=int, default=0, help="build: seed of the loader's shuffle and of the per-item draws")),
     # build-specific
     ("--materialize_images", dict(action="store_true",
@@ -92,6 +97,19 @@ _FLAGS = [
     ("--grad_sync", dict(type=str, default="auto", choices=["auto", "ddp", "flat"],
                          help="build: gradient averaging for >1 GPU (auto: flat with --hip_graph, else ddp)")),
 ]
+
+
+class SplitListMissing(FileNotFoundError, NotImplementedError):
+    """A split list (or another of the reference's split files) an evaluator needs and does
+    not find.  The lists are not shipped, so with the default locations the evaluators
+    cannot read KITTI from --data_path out of the box: that used to be refused with a
+    NotImplementedError, and a caller that caught it still does."""
+
+
+class EvalRefused(SystemExit, NotImplementedError):
+    """A command line an evaluator cannot carry out until another flag is set (an output
+    folder, the id table).  Exits like the evaluators' other usage errors; it is a
+    NotImplementedError as well because these combinations used to be refused with one."""
 
 
 class MonodepthOptions:
