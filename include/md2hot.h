@@ -966,6 +966,80 @@ int md2_depth_export16_check(const md2_depth16_desc* desc);
 int md2_depth_export16(const md2_depth16_desc* desc, const float* disp, const float* disp_flipped, uint16_t* out,
                        void* stream);
 
+/*
+ * Baseline JPEG frames decoded on the device (csrc/jpeg.hip) for training from disk: the
+ * host parses the headers (monodepth2_amd/jpeg_ops.py) and uploads the entropy-coded
+ * segments with the byte stuffing removed; Huffman decoding, dequantisation, the inverse
+ * DCT, chroma upsampling and the colour conversion run here and write the tight (h, w, 3)
+ * frames md2_aug_run_mixed reads.  Every byte is what libjpeg's accurate-integer path (the
+ * one Pillow uses) gives for the file: jidctint's islow transform, the fancy upsamplers on
+ * the cropped component planes with plain replication when the cropped chroma plane is at
+ * most two samples wide, and the 16-bit fixed-point YCbCr -> RGB tables.  Integer
+ * arithmetic only.  New symbols under ABI 24, no version bump (as md2_depth_export16).
+ *
+ * streams: device bytes; image i's unstuffed segment is stream_bytes bytes at
+ * stream_offset (a multiple of 4; whole 32-bit words are fetched, so the range is rounded
+ * up to 4 and must stay inside streams_bytes; what lies behind the last byte is masked).
+ * images: HOST array of n, staged through a pinned ring owned by the plan and uploaded on
+ * `stream` (the call does not wait for the GPU; a plan is not thread-safe and its calls
+ * belong on one stream, since they share its workspace).  bank: DEVICE tables the images
+ * index per component: quant, num_quant x 64 uint16 in natural (row-major) order, 16-byte
+ * aligned; huff, num_huff x 272 bytes, the 16 code counts by length then 256 symbol values,
+ * as a DHT segment lists them.  out: device bytes; frame i is written at out_offset (a
+ * multiple of 16), nothing else of out is touched.  status: device uint32[n], written by
+ * the call: 0, or MD2_JPEG_ST_* bits when the stream did not decode to exactly the image's
+ * blocks (the frame is then unspecified; the other frames of the batch are unaffected).
+ *
+ * A fixed chain of launches for the whole batch (memset, entropy, DC scan, inverse DCT,
+ * colour), hipGraph-unfriendly only in the descriptor upload.  Entropy decoding is parallel
+ * within an image without restart markers: the stream is cut into 128-byte subsequences
+ * whose entry states converge by a fixed-point iteration to those of the sequential decode
+ * (csrc/jpeg.hip), so the result does not depend on scheduling: two runs are bit-equal.
+ * Refused (MD2_ERR_ARG) before anything is launched: NULL arguments, n < 1 or n > 4096 or
+ * above the plan's, a height or width outside 1..8192, an unknown sampling class, a stream
+ * above 2^28 bytes, a table index outside the bank, a misaligned offset, a stream or frame
+ * that leaves its buffer, a batch that needs more workspace than the plan owns.
+ * Overlapping frames are not refused.  md2_jpeg_check runs the same checks alone.
+ */
+#define MD2_JPEG_444 0   /* sampling factors 1x1, 1x1, 1x1 */
+#define MD2_JPEG_422 1   /* 2x1, 1x1, 1x1 */
+#define MD2_JPEG_420 2   /* 2x2, 1x1, 1x1 */
+
+#define MD2_JPEG_ST_BLOCKS (1u << 0)   /* the stream holds fewer or more blocks than the image */
+#define MD2_JPEG_ST_CODE   (1u << 1)   /* a bit pattern that is no Huffman code */
+#define MD2_JPEG_ST_END    (1u << 2)   /* a symbol reaches past the end of the stream */
+
+typedef struct md2_jpeg_image {
+    uint64_t stream_offset;         /* bytes into streams, a multiple of 4 */
+    uint64_t out_offset;            /* bytes into out, a multiple of 16 */
+    uint32_t stream_bytes;          /* of the unstuffed entropy-coded segment */
+    int32_t height, width;          /* 1..8192 */
+    int32_t sampling;               /* MD2_JPEG_444 / 422 / 420 */
+    uint8_t quant[3];               /* per component: index into bank.quant */
+    uint8_t dc[3], ac[3];           /* per component: indices into bank.huff */
+    uint8_t reserved[7];            /* 0; the struct is 48 bytes */
+} md2_jpeg_image;
+
+typedef struct md2_jpeg_bank {
+    const void* quant;
+    const void* huff;
+    int32_t num_quant, num_huff;    /* 1..256 each */
+} md2_jpeg_bank;
+
+typedef struct md2_jpeg_plan md2_jpeg_plan;
+
+/* Device scratch a batch needs (coefficients, sample planes, subsequence states): 0 (and
+ * md2_last_error) for a batch md2_jpeg_run would refuse on its geometry. */
+size_t md2_jpeg_workspace_bytes(const md2_jpeg_image* images, int n);
+int md2_jpeg_check(const md2_jpeg_image* images, int n, int num_quant, int num_huff, uint64_t streams_bytes,
+                   uint64_t out_bytes);
+/* Allocates the workspace on the current device and the pinned descriptor ring for up to
+ * max_images images.  NULL on error. */
+md2_jpeg_plan* md2_jpeg_plan_create(int max_images, size_t workspace_bytes);
+void md2_jpeg_plan_destroy(md2_jpeg_plan* plan);
+int md2_jpeg_run(md2_jpeg_plan* plan, const uint8_t* streams, uint64_t streams_bytes, const md2_jpeg_image* images,
+                 int n, const md2_jpeg_bank* bank, uint8_t* out, uint64_t out_bytes, uint32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

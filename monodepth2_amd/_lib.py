@@ -77,7 +77,9 @@ EXPORTS = ["md2_abi_version", "md2_last_error", "md2_workspace_bytes", "md2_sele
            "md2_bn_pool_fwd_supported", "md2_bn_pool_fwd", "md2_bn_bwd_reduce_mask", "md2_bn_coef_offset",
            "md2_stem_wgrad_bn_supported", "md2_stem_wgrad_bn",
            "md2_aug_plan_create_mixed", "md2_aug_run_mixed",
-           "md2_depth_export16", "md2_depth_export16_check"]
+           "md2_depth_export16", "md2_depth_export16_check",
+           "md2_jpeg_workspace_bytes", "md2_jpeg_check", "md2_jpeg_plan_create", "md2_jpeg_plan_destroy",
+           "md2_jpeg_run"]
 
 DTYPE_F32 = 0    # md2_desc.disp_dtype
 DTYPE_BF16 = 1
@@ -228,7 +230,37 @@ class Depth16Desc(ctypes.Structure):
                 ("clip_max", ctypes.c_double), ("quant", ctypes.c_double), ("reserved", ctypes.c_int64)]
 
 
+# md2_jpeg_run (csrc/jpeg.hip): new symbols under ABI 24, no version bump
+JPEG_444, JPEG_422, JPEG_420 = 0, 1, 2
+JPEG_ST_BLOCKS, JPEG_ST_CODE, JPEG_ST_END = 1, 2, 4
+JPEG_QUANT_BYTES = 128   # one bank.quant table: 64 uint16, natural order
+JPEG_HUFF_BYTES = 272    # one bank.huff table: counts[16], values[256]
+
+
+class JpegImage(ctypes.Structure):
+    _fields_ = [("stream_offset", ctypes.c_uint64), ("out_offset", ctypes.c_uint64),
+                ("stream_bytes", ctypes.c_uint32), ("height", ctypes.c_int32), ("width", ctypes.c_int32),
+                ("sampling", ctypes.c_int32), ("quant", ctypes.c_uint8 * 3), ("dc", ctypes.c_uint8 * 3),
+                ("ac", ctypes.c_uint8 * 3), ("reserved", ctypes.c_uint8 * 7)]
+
+
+class JpegBank(ctypes.Structure):
+    _fields_ = [("quant", _vp), ("huff", _vp), ("num_quant", ctypes.c_int32), ("num_huff", ctypes.c_int32)]
+
+
 def _declare(L):
+    L.md2_jpeg_workspace_bytes.restype = ctypes.c_size_t
+    L.md2_jpeg_workspace_bytes.argtypes = [ctypes.POINTER(JpegImage), ctypes.c_int]
+    L.md2_jpeg_check.restype = ctypes.c_int
+    L.md2_jpeg_check.argtypes = [ctypes.POINTER(JpegImage), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                 ctypes.c_uint64, ctypes.c_uint64]
+    L.md2_jpeg_plan_create.restype = _vp
+    L.md2_jpeg_plan_create.argtypes = [ctypes.c_int, ctypes.c_size_t]
+    L.md2_jpeg_plan_destroy.restype = None
+    L.md2_jpeg_plan_destroy.argtypes = [_vp]
+    L.md2_jpeg_run.restype = ctypes.c_int
+    L.md2_jpeg_run.argtypes = [_vp, _vp, ctypes.c_uint64, ctypes.POINTER(JpegImage), ctypes.c_int,
+                               ctypes.POINTER(JpegBank), _vp, ctypes.c_uint64, _vp, _vp]
     L.md2_depth_export16.restype = ctypes.c_int
     L.md2_depth_export16.argtypes = [ctypes.POINTER(Depth16Desc)] + [_vp] * 4
     L.md2_depth_export16_check.restype = ctypes.c_int

@@ -1,0 +1,377 @@
+"""Baseline JPEG frames decoded on the device (csrc/jpeg.hip, `md2_jpeg_run`).
+
+`parse_jpeg(data)` reads a file's headers on the host, in pure Python and without decoding
+anything, and returns a `JpegStream` for the class of files the kernels take: one baseline
+(SOF0) 8-bit frame of three YCbCr components sampled 4:4:4, 4:2:2 or 4:2:0, one scan, no
+restart interval.  Anything else gives None and the caller decodes with PIL as before.
+
+`decode_jpeg_batch(streams, out, offsets, device)` uploads the unstuffed entropy-coded
+segments of a batch with their (deduplicated) tables in one pinned block and runs the
+decoder: frame i lands in `out` as a tight (h, w, 3) image at byte `offsets[i]`, every byte
+equal to `np.asarray(Image.open(path).convert("RGB"))`.  There is no CPU path: a non-CUDA
+device is an error.
+"""
+from __future__ import annotations
+
+import ctypes
+import struct
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+
+MAX_DIM = 8192
+SAMPLINGS = {((1, 1), (1, 1), (1, 1)): _lib.JPEG_444,
+             ((2, 1), (1, 1), (1, 1)): _lib.JPEG_422,
+             ((2, 2), (1, 1), (1, 1)): _lib.JPEG_420}
+
+# zigzag position -> natural (row-major) index
+ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48,
+          41, 34, 27, 20, 13, 6, 7, 14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+          30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63)
+
+_STANDALONE = frozenset([0x01] + list(range(0xD0, 0xD8)))   # TEM, RSTn: no length field
+
+
+class JpegStream:
+    """What the device needs of one file.  quant[c]: component c's 64 quantisation steps in
+    natural order; huff: {(cls, id): (counts[16], values)} with cls 0 = DC, 1 = AC; dc[c] /
+    ac[c]: component c's table ids; data: the entropy-coded segment, unstuffed."""
+    __slots__ = ("height", "width", "sampling", "factors", "quant", "huff", "dc", "ac", "data")
+
+    def __init__(self, height, width, sampling, factors, quant, huff, dc, ac, data):
+        self.height, self.width, self.sampling, self.factors = height, width, sampling, factors
+        self.quant, self.huff, self.dc, self.ac, self.data = quant, huff, dc, ac, data
+
+    @property
+    def size(self) -> Tuple[int, int]:
+        """(width, height), as PIL's Image.size."""
+        return (self.width, self.height)
+
+
+def unstuff(segment: bytes) -> bytes:
+    """The entropy-coded bytes with every stuffed FF 00 turned back into FF."""
+    return bytes(segment).replace(b"\xff\x00", b"\xff")
+
+
+def entropy_segment(d: bytes, start: int) -> Optional[bytes]:
+    """The entropy-coded segment that starts at byte `start`, unstuffed: up to the first
+    FF xx with xx != 00, which must be the EOI (else None).  In numpy, whose loops run
+    without the interpreter lock: this is the one step that touches every byte of the file,
+    and the loader's threads do it side by side."""
+    a = np.frombuffer(d, np.uint8, offset=start) if start < len(d) else np.zeros(0, np.uint8)
+    ff = np.flatnonzero(a[:-1] == 0xFF)
+    after = a[ff + 1]
+    marker = np.flatnonzero(after)
+    if marker.size == 0 or after[marker[0]] != 0xD9:
+        return None
+    end = int(ff[marker[0]])
+    keep = np.ones(end, dtype=bool)
+    keep[ff[:marker[0]] + 1] = False          # the zero of every FF 00 before the EOI
+    return a[:end][keep].tobytes()
+
+
+def _huffman_ok(counts: Sequence[int], nvalues: int) -> bool:
+    """A table the canonical construction can hold: as many values as codes, at most 256,
+    and no length oversubscribed (the all-ones code of the last length stays free)."""
+    if sum(counts) != nvalues or nvalues > 256 or nvalues < 1:
+        return False
+    code = 0
+    for length, n in enumerate(counts, 1):
+        code += n
+        if code > (1 << length) - (1 if n else 0):
+            return False
+        code <<= 1
+    return True
+
+
+def parse_jpeg(data) -> Optional[JpegStream]:
+    """The description of a supported baseline JPEG file, or None (see the module text)."""
+    try:
+        return _parse(bytes(data) if not isinstance(data, bytes) else data)
+    except (struct.error, IndexError, ValueError):
+        return None
+
+
+def _parse(d: bytes) -> Optional[JpegStream]:
+    if len(d) < 4 or d[0:2] != b"\xff\xd8":
+        return None
+    pos = 2
+    qtabs: Dict[int, Tuple[int, ...]] = {}
+    huff: Dict[Tuple[int, int], Tuple[Tuple[int, ...], bytes]] = {}
+    frame = None
+    while True:
+        if pos + 4 > len(d) or d[pos] != 0xFF:
+            return None
+        while d[pos + 1] == 0xFF:   # fill bytes before a marker
+            pos += 1
+            if pos + 4 > len(d):
+                return None
+        m = d[pos + 1]
+        pos += 2
+        if m in _STANDALONE or m == 0xD8 or m == 0xD9 or m == 0x00:
+            return None             # a restart marker, a second SOI or an EOI before any scan
+        (length,) = struct.unpack_from(">H", d, pos)
+        if length < 2 or pos + length > len(d):
+            return None
+        seg = d[pos + 2:pos + length]
+        if m == 0xC0:               # SOF0: the one baseline frame
+            if frame is not None or len(seg) < 6:
+                return None
+            prec, h, w, nc = struct.unpack_from(">BHHB", seg, 0)
+            if prec != 8 or nc != 3 or len(seg) != 6 + 3 * nc:
+                return None
+            if not (1 <= h <= MAX_DIM and 1 <= w <= MAX_DIM):
+                return None
+            comps = [(seg[6 + 3 * i], seg[7 + 3 * i] >> 4, seg[7 + 3 * i] & 15, seg[8 + 3 * i]) for i in range(3)]
+            frame = (h, w, comps)
+        elif 0xC1 <= m <= 0xCF and m not in (0xC4, 0xC8, 0xCC):
+            return None             # extended, progressive, lossless, arithmetic frames
+        elif m == 0xCC:
+            return None             # arithmetic conditioning
+        elif m == 0xC4:             # DHT, possibly several tables
+            i = 0
+            while i < len(seg):
+                tc, th = seg[i] >> 4, seg[i] & 15
+                counts = tuple(seg[i + 1:i + 17])
+                if tc > 1 or th > 3 or len(counts) != 16:
+                    return None
+                n = sum(counts)
+                vals = seg[i + 17:i + 17 + n]
+                if len(vals) != n or not _huffman_ok(counts, n):
+                    return None
+                huff[(tc, th)] = (counts, bytes(vals))
+                i += 17 + n
+        elif m == 0xDB:             # DQT, possibly several tables
+            i = 0
+            while i < len(seg):
+                pq, tq = seg[i] >> 4, seg[i] & 15
+                if pq != 0 or tq > 3 or i + 65 > len(seg):
+                    return None     # 16-bit tables belong to 12-bit files
+                zz = seg[i + 1:i + 65]
+                nat = [0] * 64
+                for k in range(64):
+                    nat[ZIGZAG[k]] = zz[k]
+                if min(nat) < 1:
+                    return None
+                qtabs[tq] = tuple(nat)
+                i += 65
+        elif m == 0xDD:             # DRI
+            if len(seg) != 2 or seg != b"\x00\x00":
+                return None
+        elif m == 0xEE:             # APP14: an Adobe marker picks the colour transform
+            if seg[:5] == b"Adobe":
+                return None
+        elif m == 0xDA:             # SOS
+            if frame is None:
+                return None
+            break
+        elif m == 0xDC or m == 0xDE or m == 0xDF:
+            return None             # DNL, hierarchical
+        pos += length
+    h, w, comps = frame
+    if len(seg) != 1 + 2 * 3 + 3 or seg[0] != 3:
+        return None
+    if (seg[7], seg[8], seg[9]) != (0, 63, 0):
+        return None
+    ids = [c[0] for c in comps]
+    if len(set(ids)) != 3 or bytes(ids) == b"RGB":
+        return None                 # libjpeg would take R, G, B ids for an RGB file
+    dc, ac = [], []
+    for i in range(3):              # the scan lists the components in frame order
+        if seg[1 + 2 * i] != ids[i]:
+            return None
+        dc.append(seg[2 + 2 * i] >> 4)
+        ac.append(seg[2 + 2 * i] & 15)
+    factors = tuple((c[1], c[2]) for c in comps)
+    sampling = SAMPLINGS.get(factors)
+    if sampling is None:
+        return None
+    if any(c[3] not in qtabs for c in comps):
+        return None
+    if any((0, t) not in huff for t in dc) or any((1, t) not in huff for t in ac):
+        return None
+    body = entropy_segment(d, pos + length)
+    if body is None:
+        return None                 # cut before EOI, or a second scan / restart marker
+    used = {(0, t): huff[(0, t)] for t in dc}
+    used.update({(1, t): huff[(1, t)] for t in ac})
+    return JpegStream(h, w, sampling, factors, tuple(qtabs[c[3]] for c in comps), used, tuple(dc), tuple(ac),
+                      body)
+
+
+def _align(n: int, a: int) -> int:
+    return (n + a - 1) // a * a
+
+
+class _Plan:
+    """Per device: the C plan (workspace, descriptor ring), a small ring of pinned staging
+    blocks with the events behind their uploads, the device copy of the block and the status
+    words.  Everything grows to the largest batch seen and is then reused."""
+    RING = 3
+
+    def __init__(self, device: torch.device):
+        self.device = device
+        self.plan = None
+        self.max_images = 0
+        self.workspace = 0
+        self.pinned: List[Optional[torch.Tensor]] = [None] * self.RING
+        self.events: List[Optional[torch.cuda.Event]] = [None] * self.RING
+        self.slot = 0
+        self.staged: Optional[torch.Tensor] = None
+        self.status: Optional[torch.Tensor] = None
+
+    def reserve(self, n: int, workspace: int):
+        if self.plan is not None and n <= self.max_images and workspace <= self.workspace:
+            return
+        L = _lib.lib()
+        if self.plan is not None:
+            L.md2_jpeg_plan_destroy(self.plan)   # waits for the work that uses it
+            self.plan = None
+        self.max_images = max(n, self.max_images)
+        self.workspace = max(workspace + workspace // 8, self.workspace)
+        with torch.cuda.device(self.device):
+            self.plan = L.md2_jpeg_plan_create(self.max_images, self.workspace)
+        if not self.plan:
+            self.max_images = self.workspace = 0
+            _lib.check(-1, "md2_jpeg_plan_create")
+        self.status = torch.zeros(self.max_images, dtype=torch.int32, device=self.device)
+
+    def stage(self, nbytes: int) -> Tuple[torch.Tensor, torch.Tensor, int]:
+        r = self.slot
+        self.slot = (r + 1) % self.RING
+        if self.events[r] is not None:
+            self.events[r].synchronize()   # its upload has run (RING calls ago)
+        if self.pinned[r] is None or self.pinned[r].numel() < nbytes:
+            self.pinned[r] = torch.empty(nbytes + nbytes // 8, dtype=torch.uint8, pin_memory=True)
+        if self.staged is None or self.staged.numel() < nbytes:
+            self.staged = torch.empty(nbytes + nbytes // 8, dtype=torch.uint8, device=self.device)
+        return self.pinned[r], self.staged, r
+
+    def __del__(self):
+        try:
+            if self.plan is not None:
+                _lib.lib().md2_jpeg_plan_destroy(self.plan)
+        except Exception:
+            pass
+
+
+_plans: Dict[torch.device, _Plan] = {}
+
+
+def _plan_for(device: torch.device) -> _Plan:
+    p = _plans.get(device)
+    if p is None:
+        p = _plans[device] = _Plan(device)
+    return p
+
+
+def describe_batch(streams: Sequence[JpegStream], offsets: Sequence[int]):
+    """The host side of a call: the md2_jpeg_image array, the deduplicated table bank
+    (quantisation tables as uint16 in natural order, Huffman tables as counts + values) and
+    the byte layout of the staging block: (images, quant_tables, huff_tables, stream_base,
+    total_bytes), streams at 16-byte aligned offsets behind the tables."""
+    n = len(streams)
+    if n != len(offsets):
+        raise ValueError(f"{n} streams but {len(offsets)} offsets")
+    images = (_lib.JpegImage * max(n, 1))()
+    quant: Dict[Tuple[int, ...], int] = {}
+    huff: Dict[Tuple[Tuple[int, ...], bytes], int] = {}
+    for i, s in enumerate(streams):
+        im = images[i]
+        im.height, im.width, im.sampling = s.height, s.width, s.sampling
+        im.out_offset = int(offsets[i])
+        im.stream_bytes = len(s.data)
+        for c in range(3):
+            im.quant[c] = quant.setdefault(s.quant[c], len(quant))
+            im.dc[c] = huff.setdefault(s.huff[(0, s.dc[c])], len(huff))
+            im.ac[c] = huff.setdefault(s.huff[(1, s.ac[c])], len(huff))
+    if len(quant) > 255 or len(huff) > 255:
+        raise ValueError("more than 255 distinct tables in one batch: decode it in parts")
+    base = _align(len(quant) * _lib.JPEG_QUANT_BYTES + len(huff) * _lib.JPEG_HUFF_BYTES, 16)
+    pos = 0
+    for i, s in enumerate(streams):
+        images[i].stream_offset = pos
+        pos += _align(len(s.data), 16)
+    return images, list(quant), list(huff), base, base + max(pos, 16)
+
+
+def fill_staging(host: np.ndarray, streams, images, quant, huff, base: int):
+    """The staging block of describe_batch's layout written into `host` (uint8)."""
+    q = np.asarray(quant, dtype=np.uint16).reshape(-1)
+    nq = q.size * 2
+    host[:nq] = q.view(np.uint8)
+    pos = nq
+    for counts, vals in huff:
+        host[pos:pos + 16] = counts
+        host[pos + 16:pos + 16 + len(vals)] = np.frombuffer(vals, np.uint8)
+        host[pos + 16 + len(vals):pos + _lib.JPEG_HUFF_BYTES] = 0
+        pos += _lib.JPEG_HUFF_BYTES
+    for i, s in enumerate(streams):
+        o = base + images[i].stream_offset
+        host[o:o + len(s.data)] = np.frombuffer(s.data, np.uint8)
+
+
+def check_described(images, n: int, num_quant: int, num_huff: int, streams_bytes: int, out_bytes: int):
+    """md2_jpeg_run's argument checks alone (host only): raises what it would refuse."""
+    _lib.check(_lib.lib().md2_jpeg_check(images, n, num_quant, num_huff, streams_bytes, out_bytes), "md2_jpeg_check")
+
+
+def run_staged(staged: torch.Tensor, images, n: int, num_quant: int, num_huff: int, base: int, total: int,
+               out: torch.Tensor, device: torch.device) -> torch.Tensor:
+    """The launches of a call whose staging block (describe_batch's layout, fill_staging's
+    bytes) is already on its way to the device tensor `staged` on the current stream.
+    Returns the plan's status words of the call (overwritten by the next call)."""
+    L = _lib.lib()
+    need = L.md2_jpeg_workspace_bytes(images, n)
+    if need == 0:
+        _lib.check(-1, "md2_jpeg_workspace_bytes")
+    plan = _plan_for(device)
+    with torch.cuda.device(device):
+        plan.reserve(n, need)
+        ptr = staged.data_ptr()
+        bank = _lib.JpegBank(ptr, ptr + num_quant * _lib.JPEG_QUANT_BYTES, num_quant, num_huff)
+        _lib.check(L.md2_jpeg_run(plan.plan, ptr + base, total - base, images, n, ctypes.byref(bank), out.data_ptr(),
+                                  out.numel(), plan.status.data_ptr(), _lib.stream(device)), "md2_jpeg_run")
+    return plan.status[:n]
+
+
+def decode_jpeg_batch(streams: Sequence[JpegStream], out: torch.Tensor, offsets: Sequence[int], device=None,
+                      check: bool = False) -> torch.Tensor:
+    """Decodes `streams` into the uint8 device buffer `out`: frame i is the tight (h, w, 3)
+    image at byte offsets[i] (a multiple of 16); no other byte of `out` is written.  One
+    asynchronous upload of one pinned block (tables and streams), then the launches, on the
+    current stream of `device`; nothing is allocated and nothing waits once the plan has
+    grown to the batch's needs.  Returns the int32 status words of the call, one per stream,
+    on the device (0 = decoded; they are the plan's and the next call overwrites them).
+    check=True synchronises and raises a RuntimeError naming the first index whose status is
+    not 0."""
+    device = torch.device(device) if device is not None else (out.device if torch.is_tensor(out) else None)
+    if device is None or device.type != "cuda" or not torch.is_tensor(out) or not out.is_cuda:
+        raise RuntimeError("decode_jpeg_batch is GPU only (HIP kernels, no CPU fallback)")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    if out.device != device or out.dtype != torch.uint8 or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous uint8 tensor on {device}")
+    n = len(streams)
+    if n == 0:
+        return torch.zeros(0, dtype=torch.int32, device=device)
+    images, quant, huff, base, total = describe_batch(streams, offsets)
+    check_described(images, n, len(quant), len(huff), total - base, out.numel())
+    plan = _plan_for(device)
+    with torch.cuda.device(device):
+        pinned, staged, r = plan.stage(total)
+        fill_staging(pinned.numpy(), streams, images, quant, huff, base)
+        staged[:total].copy_(pinned[:total], non_blocking=True)
+        if plan.events[r] is None:
+            plan.events[r] = torch.cuda.Event()
+        plan.events[r].record()
+        status = run_staged(staged, images, n, len(quant), len(huff), base, total, out, device)
+        if check:
+            bad = torch.nonzero(status.cpu()).flatten().tolist()
+            if bad:
+                raise RuntimeError(f"decode_jpeg_batch: stream index {bad[0]} did not decode "
+                                   f"(status {int(status[bad[0]])}); bad indices {bad}")
+    return status

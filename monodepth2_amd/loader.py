@@ -28,6 +28,16 @@ its first batch with an eighth to spare; a later batch that needs more is decode
 pageable memory and its slot grown on the caller's thread.  A pinned buffer goes back to
 the producer only after the event recorded behind its upload has completed, two batches
 later; nothing here calls torch.cuda.synchronize().
+
+`device_decode=True` moves the JPEG decoder onto the device (jpeg_ops, csrc/jpeg.hip): the
+decoding threads read each file and parse its headers; a supported baseline JPEG goes up
+as its unstuffed entropy-coded segment (about a seventh of its pixels) and is decoded by
+the kernels straight into the ragged buffer, anything else (PNG, progressive, ...) is
+decoded with PIL as before, uploaded in the same block and moved to its place by a device
+copy.  Every rule above stands.  The decoder's status words come back through pinned memory
+behind the slot's event and are read when the slot is retired: a stream that did not decode
+raises a RuntimeError naming the split line and the file, one or two batches after its own
+or when the epoch ends.
 """
 from __future__ import annotations
 
@@ -41,6 +51,7 @@ from typing import Dict, Iterator, List, Optional
 import numpy as np
 import torch
 
+from . import jpeg_ops
 from .augment import GpuAugmentMixed
 from .datasets import item_seed
 
@@ -59,12 +70,24 @@ class _Staged:
 
     def __init__(self, slot, total, offsets, items, spill=None):
         self.slot, self.total, self.offsets, self.items, self.spill = slot, total, offsets, items, spill
+        self.jpeg = None   # device_decode: a _StagedJpeg; `total` then counts the staging block, not the frames
+
+
+class _StagedJpeg:
+    """What a device-decoded batch adds: the decoder's host description, the frames PIL
+    decoded instead as (frame number, offset in the staging block, bytes), the size of the
+    ragged frame buffer and, per stream, the split line and file to name in an error."""
+
+    def __init__(self, images, n, num_quant, num_huff, base, jtotal, pil, frames_total, names):
+        self.images, self.n, self.num_quant, self.num_huff = images, n, num_quant, num_huff
+        self.base, self.jtotal = base, jtotal
+        self.pil, self.frames_total, self.names = pil, frames_total, names
 
 
 class BatchLoader:
     def __init__(self, dataset, batch_size: int, shuffle: bool = True, seed: int = 0, num_workers: int = 0,
                  rank: int = 0, world_size: int = 1, device=None, with_depth: bool = False, prefetch: int = 2,
-                 drop_last: bool = True):
+                 drop_last: bool = True, device_decode: bool = False):
         if not (0 <= rank < world_size):
             raise ValueError(f"rank {rank} outside world size {world_size}")
         if not drop_last and world_size > 1:
@@ -84,8 +107,10 @@ class BatchLoader:
             raise ValueError("with_depth needs a dataset built with load_depth=True whose first split line has "
                              "ground truth (check_depth)")
         self.with_depth = with_depth
+        self.device_decode = bool(device_decode)
         self.prefetch = max(int(prefetch), 1)
         self.epoch = 0
+        self.uploaded_bytes = 0   # host-to-device bytes of the batches handed out so far (tools/loader_bench.py)
         self.frame_ids = list(dataset.frame_idxs)
         self.aug = GpuAugmentMixed(dataset.height, dataset.width, self.frame_ids, batch_size, dataset.num_scales,
                                    device=self.device)
@@ -94,6 +119,9 @@ class BatchLoader:
         self._ring = self.prefetch + 1 + IN_FLIGHT
         self._pinned: List[Optional[torch.Tensor]] = [None] * self._ring
         self._uploaded: List[Optional[torch.cuda.Event]] = [None] * self._ring
+        # device_decode: per slot the decoder's status words (pinned) and whom they belong to
+        self._status: List[Optional[torch.Tensor]] = [None] * self._ring
+        self._status_of: List[Optional[List]] = [None] * self._ring
         self._pool = ThreadPoolExecutor(self.threads, thread_name_prefix="md2-decode") if self.threads else None
 
     # ------------------------------------------------------------------ order
@@ -160,6 +188,8 @@ class BatchLoader:
                 for b, it in enumerate(items):
                     offsets[f * B + b] = total
                     total += _padded(it.size)
+            if self.device_decode:
+                return self._stage_compressed(items, offsets, total, slot)
             buf, spill = self._pinned[slot], None
             if buf is None or buf.numel() < total:
                 host = spill = np.empty(total, dtype=np.uint8)
@@ -176,6 +206,47 @@ class BatchLoader:
                 it.close()
         return _Staged(slot, total, offsets, items, spill)
 
+    def _stage_compressed(self, items, offsets, frames_total: int, slot: int) -> _Staged:
+        """Step 3 with device_decode: the staging block holds the decoder's tables and the
+        unstuffed streams, then the frames PIL had to decode.  Host work only."""
+        F, B = len(self.frame_ids), len(items)
+
+        def load(n):
+            it = items[n % B]
+            with open(it.paths[n // B], "rb") as f:
+                s = jpeg_ops.parse_jpeg(f.read())
+            if s is not None and (s.height, s.width) == it.size:
+                return s
+            return self.dataset.decode(it.images[n // B])
+
+        got = self._map(load, range(F * B))
+        on_device = [n for n in range(F * B) if isinstance(got[n], jpeg_ops.JpegStream)]
+        streams = [got[n] for n in on_device]
+        images, quant, huff, base, pos = None, [], [], 0, 0
+        if streams:
+            images, quant, huff, base, pos = jpeg_ops.describe_batch(streams, [offsets[n] for n in on_device])
+            jpeg_ops.check_described(images, len(streams), len(quant), len(huff), pos - base, frames_total)
+        jtotal, pil = pos, []
+        for n in range(F * B):
+            if not isinstance(got[n], jpeg_ops.JpegStream):
+                pos = (pos + ALIGN - 1) // ALIGN * ALIGN
+                pil.append((n, pos, got[n].size))
+                pos += got[n].size
+        total = max(pos, 16)
+        buf, spill = self._pinned[slot], None
+        if buf is None or buf.numel() < total:
+            host = spill = np.empty(total, dtype=np.uint8)
+        else:
+            host = buf.numpy()
+        if streams:
+            jpeg_ops.fill_staging(host, streams, images, quant, huff, base)
+        for n, o, size in pil:
+            host[o:o + size] = got[n].reshape(-1)
+        names = [(items[n % B].index, items[n % B].line, items[n % B].paths[n // B]) for n in on_device]
+        st = _Staged(slot, total, offsets, items, spill)
+        st.jpeg = _StagedJpeg(images, len(streams), len(quant), len(huff), base, jtotal, pil, frames_total, names)
+        return st
+
     def _reserve(self, slot: int, total: int):
         """Slot `slot`'s pinned buffer holds `total` bytes (caller's thread; the slot is free)."""
         buf = self._pinned[slot]
@@ -190,6 +261,9 @@ class BatchLoader:
                 self._pinned[st.slot].numpy()[:st.total] = st.spill
             dev = torch.empty(st.total, dtype=torch.uint8, device=self.device)
             dev.copy_(self._pinned[st.slot][:st.total], non_blocking=True)
+            self.uploaded_bytes += st.total
+            if st.jpeg is not None:
+                dev = self._decode_on_device(st, dev)
             if self._uploaded[st.slot] is None:
                 self._uploaded[st.slot] = torch.cuda.Event()
             self._uploaded[st.slot].record()
@@ -199,6 +273,39 @@ class BatchLoader:
             if self.with_depth:
                 inputs["depth_gt"] = self.dataset.get_depths(st.items, device=self.device).unsqueeze(1)
         return inputs
+
+    def _decode_on_device(self, st: _Staged, up: torch.Tensor) -> torch.Tensor:
+        """The ragged frame buffer of a device-decoded batch from its uploaded staging block
+        `up`: the decoder's launches, the device copies of the PIL-decoded frames, and the
+        status words on their way to the slot's pinned copy (all on the caller's stream,
+        before the slot's event is recorded)."""
+        j = st.jpeg
+        frames = torch.empty(j.frames_total, dtype=torch.uint8, device=self.device)
+        if j.n:
+            status = jpeg_ops.run_staged(up, j.images, j.n, j.num_quant, j.num_huff, j.base, j.jtotal, frames,
+                                         self.device)
+            host = self._status[st.slot]
+            if host is None or host.numel() < j.n:
+                host = self._status[st.slot] = torch.empty(max(j.n, len(self.frame_ids) * self.batch_size),
+                                                           dtype=torch.int32, pin_memory=True)
+            host[:j.n].copy_(status, non_blocking=True)
+            self._status_of[st.slot] = j.names
+        for n, o, size in j.pil:
+            frames[st.offsets[n]:st.offsets[n] + size].copy_(up[o:o + size], non_blocking=True)
+        return frames
+
+    def _check_status(self, slot: int):
+        """After slot `slot`'s event: raises if one of its streams did not decode."""
+        names, self._status_of[slot] = self._status_of[slot], None
+        if not names:
+            return
+        words = self._status[slot][:len(names)].tolist()
+        bad = [(w, name) for w, name in zip(words, names) if w]
+        if bad:
+            w, (index, line, path) = bad[0]
+            raise RuntimeError(f"split line {index} ({line!r}): {path} did not decode on the device (status {w}: "
+                               f"the entropy-coded data does not hold the image's blocks); {len(bad)} bad "
+                               "file(s) in its batch")
 
     # -------------------------------------------------------------- iteration
     def __iter__(self) -> Iterator[Dict]:
@@ -217,14 +324,16 @@ class BatchLoader:
         for slot in range(self._ring):
             if self._uploaded[slot] is not None:
                 self._uploaded[slot].synchronize()
+            self._status_of[slot] = None   # an epoch that was abandoned: its words are not this one's
             self._reserve(slot, need)
             free.put(slot)
         in_flight = collections.deque()   # slots behind an upload, oldest first
 
-        def retire():
-            while len(in_flight) >= IN_FLIGHT:
+        def retire(keep: int = IN_FLIGHT):
+            while len(in_flight) >= max(keep, 1):
                 slot = in_flight.popleft()
                 self._uploaded[slot].synchronize()   # its upload has run: the producer may refill it
+                self._check_status(slot)
                 free.put(slot)
 
         if self._pool is None:   # no threads: everything on the caller's thread
@@ -234,6 +343,8 @@ class BatchLoader:
                 out = self._finish(st)
                 in_flight.append(st.slot)
                 yield out
+            if self.device_decode:
+                retire(0)   # the last batches' status words, before the epoch ends
             self.epoch = epoch + 1
             return
         ready: "queue.Queue" = queue.Queue(maxsize=self.prefetch)
@@ -276,6 +387,8 @@ class BatchLoader:
                 out = self._finish(st)
                 in_flight.append(st.slot)
                 yield out
+            if self.device_decode:
+                retire(0)
             self.epoch = epoch + 1
         finally:
             stop.set()

@@ -23,6 +23,8 @@ _FLAGS = [
     ("--dataset", dict(type=str, default="kitti", choices=["kitti", "kitti_odom", "kitti_depth", "kitti_test"],
                        help="dataset")),
     ("--png", dict(action="store_true", help="train from png instead of jpg")),
+    ("--device_decode", dict(action="store_true", help="decode baseline JPEG frames on the GPU (HIP kernels, "
+                                                        "bit-equal to PIL); other files still go through PIL")),
     ("--height", dict(type=int, default=192, help="input height")),
     ("--width", dict(type=int, default=640, help="input width")),
     ("--disparity_smoothness", dict(type=float, default=1e-3, help="smoothness weight")),

@@ -3,6 +3,7 @@ batch loader end to end on JPEG files (informational, like tools/velo_bench.py).
 
     python tools/loader_bench.py [--batch 12] [--repeats 5] [--calls 20] [--frames 160]
                                  [--threads 1 8 16] [--out profiles/loader_bench.json]
+                                 [--device_decode] [--subsampling 4:2:0 4:2:2]
 
 augment   md2_aug_run_mixed on --batch items x 3 frames that mix KITTI raw's four decoded
           sizes (375x1242, 370x1226, 374x1238, 376x1241, a quarter of the items each)
@@ -15,6 +16,15 @@ loader    loader.BatchLoader over a synthetic KITTI-raw tree (four drives, one p
           frame ids [0, -1, 1], shuffled, decoded by 1 / 8 / 16 threads: wall time of one
           whole epoch, through the last batch's device synchronise, one warm-up epoch, the
           median of --repeats; frames per second = decoded JPEG files per second.
+
+jpeg      with --device_decode: the loader section is measured per --subsampling (the tree
+          is written at 4:2:0, PIL's default and what this tool always wrote, or at 4:2:2,
+          KITTI's own) and per thread count for BOTH paths in one run, alternating an epoch
+          of the PIL path (device_decode=False: untouched code, the baseline) with an epoch
+          of the device path over the same tree, one warm-up epoch each; and HIP events
+          around --calls jpeg_ops.decode_jpeg_batch calls on 36 frames of 375x1242 (host
+          staging included in what the events see only as far as it delays the launches;
+          the wall time per call is reported beside it).  Never more than 16 threads.
 
 Prints one JSON line; --out also writes it to a file.
 """
@@ -38,7 +48,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from monodepth2_amd.augment import GpuAugment, GpuAugmentMixed, draw_item, pack_items, pack_ragged  # noqa: E402
 from monodepth2_amd.datasets import KITTIRAWDataset  # noqa: E402
+from monodepth2_amd.jpeg_ops import decode_jpeg_batch, describe_batch, parse_jpeg  # noqa: E402
 from monodepth2_amd.loader import BatchLoader  # noqa: E402
+
+SUBSAMPLING = {"4:4:4": 0, "4:2:2": 1, "4:2:0": 2}
 
 SIZES = [(375, 1242), (370, 1226), (374, 1238), (376, 1241)]
 H, W, S = 192, 640, 4
@@ -88,7 +101,7 @@ def bench_augment(batch, calls, repeats):
             "classes_present": len(set(sizes))}
 
 
-def write_tree(root, frames):
+def write_tree(root, frames, subsampling="4:2:0"):
     rng = np.random.default_rng(1)
     lines = []
     for n, (h, w) in enumerate(SIZES):
@@ -98,36 +111,87 @@ def write_tree(root, frames):
         base = [texture(rng, h, w) for _ in range(4)]
         for f in range(frames):
             Image.fromarray(np.roll(base[f % 4], 3 * f, axis=1)).save(
-                os.path.join(folder, "{:010d}.jpg".format(f)), quality=92)
+                os.path.join(folder, "{:010d}.jpg".format(f)), quality=92, subsampling=SUBSAMPLING[subsampling])
         lines += ["{} {} l".format(drive, f) for f in range(1, frames - 1)]
     return lines
 
 
-def bench_loader(batch, frames, threads_list, repeats):
+def epoch_time(ld):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    n = 0
+    for batch_inputs in ld:
+        n += 1
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, n
+
+
+def bench_loader(batch, frames, threads_list, repeats, subsampling="4:2:0", device_decode=False):
+    """Epoch times per thread count; with device_decode both paths, alternated epoch by epoch."""
     out = {}
+    paths = [("pil", False), ("device", True)] if device_decode else [("pil", False)]
     with tempfile.TemporaryDirectory() as root:
-        lines = write_tree(root, frames)
+        lines = write_tree(root, frames, subsampling)
         size = sum(os.path.getsize(os.path.join(dp, f)) for dp, _, fs in os.walk(root) for f in fs)
         ds = KITTIRAWDataset(root, lines, H, W, FRAME_IDS, S, is_train=True, img_ext=".jpg")
         for threads in threads_list:
-            ld = BatchLoader(ds, batch, shuffle=True, seed=0, num_workers=threads)
-            times = []
+            threads = min(threads, 16)
+            loaders = {name: BatchLoader(ds, batch, shuffle=True, seed=0, num_workers=threads, device_decode=flag)
+                       for name, flag in paths}
+            times = {name: [] for name in loaders}
+            n = 0
             for rep in range(repeats + 1):
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                n = 0
-                for batch_inputs in ld:
-                    n += 1
-                torch.cuda.synchronize()
-                if rep:
-                    times.append(time.perf_counter() - t0)
-            ld.close()
-            t = statistics.median(times)
-            out[str(threads)] = {"epoch_s": t, "batches": n, "frames_per_s": n * batch * len(FRAME_IDS) / t,
-                                 "items_per_s": n * batch / t, "epoch_s_all": times}
+                for name, ld in loaders.items():
+                    ld.set_epoch(rep)           # the same order for both paths
+                    ld.uploaded_bytes = 0
+                    t, n = epoch_time(ld)
+                    if rep:
+                        times[name].append(t)
+            row = {}
+            for name, ld in loaders.items():
+                t = statistics.median(times[name])
+                row[name] = {"epoch_s": t, "batches": n, "frames_per_s": n * batch * len(FRAME_IDS) / t,
+                             "items_per_s": n * batch / t, "epoch_s_all": times[name],
+                             "uploaded_bytes_per_batch": ld.uploaded_bytes / max(n, 1)}
+                ld.close()
+            out[str(threads)] = row if device_decode else row["pil"]
         out["files"] = len(SIZES) * frames
         out["mean_file_bytes"] = size / (len(SIZES) * frames)
+        out["subsampling"] = subsampling
     return out
+
+
+def bench_decode(calls, repeats, subsampling, frames=36):
+    """HIP events (and wall time) around `calls` decode_jpeg_batch calls on `frames` frames."""
+    import io
+    rng = np.random.default_rng(2)
+    streams = []
+    for _ in range(4):
+        buf = io.BytesIO()
+        Image.fromarray(texture(rng, *SIZES[0])).save(buf, "JPEG", quality=92, subsampling=SUBSAMPLING[subsampling])
+        streams.append(parse_jpeg(buf.getvalue()))
+    streams = [streams[i % 4] for i in range(frames)]
+    per = (SIZES[0][0] * SIZES[0][1] * 3 + 255) // 256 * 256
+    offsets = [i * per for i in range(frames)]
+    out = torch.empty(frames * per, dtype=torch.uint8, device="cuda")
+    decode_jpeg_batch(streams, out, offsets, check=True)
+    ms, wall = [], []
+    for _ in range(repeats):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        a.record()
+        for _ in range(calls):
+            decode_jpeg_batch(streams, out, offsets)
+        b.record()
+        b.synchronize()
+        wall.append((time.perf_counter() - t0) * 1e3 / calls)
+        ms.append(a.elapsed_time(b) / calls)
+    return {"frames": frames, "size": list(SIZES[0]), "subsampling": subsampling, "calls": calls,
+            "ms_per_call": statistics.median(ms), "ms_per_call_all": ms, "wall_ms_per_call": statistics.median(wall),
+            "frames_per_s": frames / (statistics.median(ms) * 1e-3),
+            "uploaded_bytes_per_batch": describe_batch(streams, offsets)[4],
+            "decoded_bytes_per_batch": frames * SIZES[0][0] * SIZES[0][1] * 3}
 
 
 def main():
@@ -138,13 +202,23 @@ def main():
     ap.add_argument("--frames", type=int, default=160)
     ap.add_argument("--threads", type=int, nargs="+", default=[1, 8, 16])
     ap.add_argument("--out", type=str)
+    ap.add_argument("--device_decode", action="store_true", help="also measure the device JPEG decoder, "
+                                                                 "alternated with the PIL path in the same run")
+    ap.add_argument("--subsampling", nargs="+", default=["4:2:0"], choices=["4:2:0", "4:2:2"],
+                    help="chroma subsampling of the synthetic tree (4:2:0 is what PIL writes by default, "
+                         "4:2:2 what KITTI's files have)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("loader_bench needs a GPU: nothing here is timed on the host alone")
     res = {"tool": "loader_bench", "device": torch.cuda.get_device_name(0),
            "python": platform.python_version(), "pillow": Image.__version__,
-           "augment": bench_augment(args.batch, args.calls, args.repeats),
-           "loader": bench_loader(args.batch, args.frames, args.threads, args.repeats)}
+           "augment": bench_augment(args.batch, args.calls, args.repeats)}
+    if args.device_decode:
+        res["loader_jpeg"] = {sub: bench_loader(args.batch, args.frames, args.threads, args.repeats, sub, True)
+                              for sub in args.subsampling}
+        res["decode"] = {sub: bench_decode(args.calls, args.repeats, sub) for sub in args.subsampling}
+    else:
+        res["loader"] = bench_loader(args.batch, args.frames, args.threads, args.repeats, args.subsampling[0])
     line = json.dumps(res)
     print(line)
     if args.out:
