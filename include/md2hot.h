@@ -1040,6 +1040,88 @@ void md2_jpeg_plan_destroy(md2_jpeg_plan* plan);
 int md2_jpeg_run(md2_jpeg_plan* plan, const uint8_t* streams, uint64_t streams_bytes, const md2_jpeg_image* images,
                  int n, const md2_jpeg_bank* bank, uint8_t* out, uint64_t out_bytes, uint32_t* status, void* stream);
 
+/*
+ * The training log's pictures (csrc/md2hot.hip): what the reference's Trainer.log writes at
+ * a log step (trainer.py:540-572, with normalize_image, utils.py:22-28) for the first
+ * `items` images of the batch, as one uint8 contact sheet (items, sheet_h, sheet_w, 3) filled
+ * on the device in two launches on `stream`: per-(item, scale) disparity minimum and maximum
+ * (one block each; its other blocks clear the sheet), then one table-driven launch that
+ * writes every tile.  New symbols under ABI 24, no version bump (as md2_jpeg_run).
+ *
+ * A tile is a rectangle of the sheet of item `item`; tiles are disjoint, everything outside
+ * them is written 0 (the caller does not clear the sheet).  Kinds, with (h_s, w_s) =
+ * (height >> s, width >> s):
+ *   MD2_LOG_COLOR  src: fp32 (3, h_s, w_s) planes, inputs[("color", frame, s)][item]; R, G, B.
+ *   MD2_LOG_WARP   outputs[("color", frame, 0)][item] (trainer.py:384-387) for source frame
+ *                  `frame` (1..S), scale 0 only, computed here from tensors->disp[0], color[0],
+ *                  K[0], inv_K[0] and T (the scale-0 T with MD2_T_PER_SCALE) with
+ *                  md2_generate_images's own device functions: bit-equal to quantising its
+ *                  color_out.  src: color[0][frame] + item * 3 * height * width.
+ *   MD2_LOG_DISP   normalize_image(outputs[("disp", s)][item]); src: that map, (h_s, w_s),
+ *                  fp32 or bf16 by desc.hot.disp_dtype (bf16 is widened exactly), and
+ *                  tensors->disp[s] must be the batch it belongs to (the statistics are
+ *                  taken from there).  With mi, ma the map's minimum and maximum:
+ *                  d = fp32(fp64(ma) - fp64(mi)), or 1e5 when ma == mi; v = (x - mi) / d,
+ *                  an fp32 subtraction and a correctly rounded fp32 division.  A map that
+ *                  holds a NaN has mi = ma = NaN and every byte 0.  Grey.
+ *   MD2_LOG_MAP    src: an fp32 (h, w) map written as grey, (h, w) = (h_s, w_s) (a predictive
+ *                  mask, trainer.py:562-567) or (height, width) (identity_selection at the
+ *                  loss resolution, trainer.py:569-572).
+ * Every value becomes a byte as the reference's image writer makes one of a float image:
+ * uint8(clip(fp32(x) * 255f, 0, 255)), one fp32 product then truncation; NaN gives 0.  So
+ * x = fp32(k / 255) gives k for every k.  Grey tiles repeat the byte in the three channels.
+ * Tiles whose x and w are multiples of 4 pixels (and sheet_w too) store whole dwords.
+ *
+ * tiles: DEVICE array of desc->num_tiles entries in ascending block0, entry e owning grid
+ * blocks [block0, block0 + md2_log_panel_tile_blocks(e)); it must be a copy of a host table
+ * that md2_log_panel_check accepted.  workspace: md2_log_panel_workspace_bytes, 256-byte
+ * aligned, no initialisation needed; after the call its first items * num_scales * 2 floats
+ * hold mi, ma per (item, scale).  sheet: 16-byte aligned.  Integer and fp32 arithmetic, no
+ * atomics: bitwise repeatable.  hipGraph-capturable, no allocation, no host synchronisation.
+ *
+ * md2_log_panel_check (host only, touches no device) answers MD2_ERR_ARG for: a NULL desc or
+ * table, non-positive sizes, num_scales outside 1..4, num_src outside 1..3, a scale whose
+ * map would be empty, items outside 1..MD2_LOG_MAX_ITEMS or above batch, num_tiles outside
+ * 1..MD2_LOG_MAX_TILES, a sheet of 2^31 bytes or more, an unknown kind, an item, scale or
+ * frame (0..S; warp: 1..S) out of range, a warp tile at a scale other than 0 or in a frame
+ * smaller than 2 x 2, a size that does not match kind, scale and desc, a tile that leaves the
+ * sheet or overlaps another tile of its item, a NULL src, a block0 that is not the running
+ * sum of md2_log_panel_tile_blocks.  tensors may be NULL when the table holds no warp tile;
+ * with one, T, disp[0], K[0], inv_K[0] and color[0][1..S] must be set.
+ */
+#define MD2_LOG_COLOR 0
+#define MD2_LOG_WARP  1
+#define MD2_LOG_DISP  2
+#define MD2_LOG_MAP   3
+#define MD2_LOG_MAX_ITEMS 4
+#define MD2_LOG_MAX_TILES 1024
+
+typedef struct md2_log_tile {
+    int32_t kind;                   /* MD2_LOG_* */
+    int32_t item;                   /* image of the batch, 0..items-1 */
+    int32_t scale;                  /* 0..num_scales-1 */
+    int32_t frame;                  /* 0 = target, 1..S = frame_ids[1:] */
+    int32_t y, x, h, w;             /* rectangle in the item's sheet, pixels */
+    const void* src;                /* see the kinds above (offset 32) */
+    int32_t block0;                 /* first grid block of this tile */
+    int32_t reserved;               /* 0; the struct is 48 bytes */
+} md2_log_tile;
+
+typedef struct md2_log_desc {
+    md2_desc hot;                   /* the step's hot-path descriptor (48 bytes) */
+    int32_t items;                  /* n = min(4, batch) */
+    int32_t sheet_h, sheet_w;
+    int32_t num_tiles;              /* the struct is 64 bytes */
+} md2_log_desc;
+
+/* grid blocks of one tile: ceil(h * ceil(w / 4) / 256), one thread per 4-pixel run of a row */
+int md2_log_panel_tile_blocks(const md2_log_tile* tile);
+int md2_log_panel_check(const md2_log_desc* desc, const md2_log_tile* tiles_host, const md2_tensors* tensors);
+/* 0 (and md2_last_error) for a desc md2_log_panel would refuse */
+size_t md2_log_panel_workspace_bytes(const md2_log_desc* desc);
+int md2_log_panel(const md2_log_desc* desc, const md2_tensors* tensors, const md2_log_tile* tiles,
+                  int total_blocks, uint8_t* sheet, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -79,7 +79,8 @@ EXPORTS = ["md2_abi_version", "md2_last_error", "md2_workspace_bytes", "md2_sele
            "md2_aug_plan_create_mixed", "md2_aug_run_mixed",
            "md2_depth_export16", "md2_depth_export16_check",
            "md2_jpeg_workspace_bytes", "md2_jpeg_check", "md2_jpeg_plan_create", "md2_jpeg_plan_destroy",
-           "md2_jpeg_run"]
+           "md2_jpeg_run",
+           "md2_log_panel_tile_blocks", "md2_log_panel_check", "md2_log_panel_workspace_bytes", "md2_log_panel"]
 
 DTYPE_F32 = 0    # md2_desc.disp_dtype
 DTYPE_BF16 = 1
@@ -248,7 +249,32 @@ class JpegBank(ctypes.Structure):
     _fields_ = [("quant", _vp), ("huff", _vp), ("num_quant", ctypes.c_int32), ("num_huff", ctypes.c_int32)]
 
 
+# md2_log_panel (csrc/md2hot.hip): new symbols under ABI 24, no version bump
+LOG_COLOR, LOG_WARP, LOG_DISP, LOG_MAP = 0, 1, 2, 3
+LOG_MAX_ITEMS = 4
+LOG_MAX_TILES = 1024
+
+
+class LogTile(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int32), ("item", ctypes.c_int32), ("scale", ctypes.c_int32),
+                ("frame", ctypes.c_int32), ("y", ctypes.c_int32), ("x", ctypes.c_int32), ("h", ctypes.c_int32),
+                ("w", ctypes.c_int32), ("src", _vp), ("block0", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class LogDesc(ctypes.Structure):
+    _fields_ = [("hot", Desc), ("items", ctypes.c_int32), ("sheet_h", ctypes.c_int32), ("sheet_w", ctypes.c_int32),
+                ("num_tiles", ctypes.c_int32)]
+
+
 def _declare(L):
+    L.md2_log_panel_tile_blocks.restype = ctypes.c_int
+    L.md2_log_panel_tile_blocks.argtypes = [ctypes.POINTER(LogTile)]
+    L.md2_log_panel_check.restype = ctypes.c_int
+    L.md2_log_panel_check.argtypes = [ctypes.POINTER(LogDesc), ctypes.POINTER(LogTile), ctypes.POINTER(Tensors)]
+    L.md2_log_panel_workspace_bytes.restype = ctypes.c_size_t
+    L.md2_log_panel_workspace_bytes.argtypes = [ctypes.POINTER(LogDesc)]
+    L.md2_log_panel.restype = ctypes.c_int
+    L.md2_log_panel.argtypes = [ctypes.POINTER(LogDesc), ctypes.POINTER(Tensors), _vp, ctypes.c_int, _vp, _vp, _vp]
     L.md2_jpeg_workspace_bytes.restype = ctypes.c_size_t
     L.md2_jpeg_workspace_bytes.argtypes = [ctypes.POINTER(JpegImage), ctypes.c_int]
     L.md2_jpeg_check.restype = ctypes.c_int

@@ -2034,6 +2034,146 @@ __global__ __launch_bounds__(kBlock) void generate_kernel(GenArgs g) {
 }
 
 // ----------------------------------------------------------------------------
+// the training log's contact sheet (md2_log_panel; reference trainer.py:540-572)
+// ----------------------------------------------------------------------------
+struct LogArgs {
+    PhotoArgs p;                 // the warp context of scale 0; disp / dh / dw of every scale
+    const md2_log_tile* tiles;   // device table, ascending block0
+    int ntiles, items, nscales;
+    int SH, SW;
+    uint8_t* sheet;              // (items, SH, SW, 3)
+    float* stats;                // (items, nscales, 2): mi, ma
+    long long sheet_bytes;
+};
+
+// Launch 1: block (item, scale) < items * nscales takes the minimum and maximum of that
+// disparity map (torch's x.min() / x.max(): a NaN anywhere makes both NaN); the blocks
+// behind them clear the sheet with 16-byte stores, its last bytes one by one.
+__global__ __launch_bounds__(kBlock) void log_stats_kernel(LogArgs g) {
+    const int nstat = g.items * g.nscales;
+    if ((int)blockIdx.x >= nstat) {
+        const long long n16 = g.sheet_bytes >> 4;
+        const long long stride = (long long)(gridDim.x - nstat) * kBlock;
+        uint4* o = (uint4*)g.sheet;
+        for (long long i = (long long)(blockIdx.x - nstat) * kBlock + threadIdx.x; i < n16; i += stride)
+            o[i] = make_uint4(0u, 0u, 0u, 0u);
+        if ((int)blockIdx.x == nstat && threadIdx.x < (unsigned)(g.sheet_bytes & 15))
+            g.sheet[(n16 << 4) + threadIdx.x] = 0;
+        return;
+    }
+    const int j = blockIdx.x / g.nscales, s = blockIdx.x - j * g.nscales;
+    const int n = g.p.dh[s] * g.p.dw[s];
+    const bool bf = g.p.disp_bf16 != 0;
+    const float* d = disp_off(g.p.disp[s], (size_t)j * n, bf);
+    float mn = INFINITY, mx = -INFINITY;
+    int nan = 0;
+    // one block walks a whole map (122880 values at 640x192): eight independent loads in
+    // flight per thread, so the walk is bound by bandwidth and not by one load's latency
+    constexpr int kU = 8;
+    for (int i0 = threadIdx.x; i0 < n; i0 += kU * kBlock) {
+        float v[kU];
+#pragma unroll
+        for (int k = 0; k < kU; ++k) {
+            const int i = i0 + k * kBlock;
+            v[k] = ldd(d, i < n ? i : i0, bf);   // past the end: the run's first value again
+        }
+#pragma unroll
+        for (int k = 0; k < kU; ++k) {
+            nan |= (v[k] != v[k]) ? 1 : 0;
+            mn = fminf(mn, v[k]);
+            mx = fmaxf(mx, v[k]);
+        }
+    }
+    __shared__ float smn[kBlock], smx[kBlock];
+    __shared__ int snan[kBlock];
+    smn[threadIdx.x] = mn;
+    smx[threadIdx.x] = mx;
+    snan[threadIdx.x] = nan;
+    __syncthreads();
+    for (int o = kBlock / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            smn[threadIdx.x] = fminf(smn[threadIdx.x], smn[threadIdx.x + o]);
+            smx[threadIdx.x] = fmaxf(smx[threadIdx.x], smx[threadIdx.x + o]);
+            snan[threadIdx.x] |= snan[threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        g.stats[2 * blockIdx.x + 0] = snan[0] ? NAN : smn[0];
+        g.stats[2 * blockIdx.x + 1] = snan[0] ? NAN : smx[0];
+    }
+}
+
+// uint8(clip(fp32(x) * 255f, 0, 255)): one product, truncation, NaN -> 0 (fmaxf drops it)
+__device__ __forceinline__ uint32_t log_byte(float x) {
+    return (uint32_t)fminf(fmaxf(x * 255.0f, 0.f), 255.0f);
+}
+__device__ __forceinline__ uint32_t log_grey(float x) { return log_byte(x) * 0x010101u; }
+
+// Launch 2: one thread per run of 4 pixels of a tile row.  Block b belongs to the last
+// tile whose block0 <= b (md2_conv_split_weights_multi's search, on the scalar path).
+__global__ __launch_bounds__(kBlock) void log_panel_kernel(LogArgs g) {
+    const int b = blockIdx.x;
+    int lo = 0, hi = g.ntiles - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (g.tiles[mid].block0 <= b) lo = mid;
+        else hi = mid - 1;
+    }
+    const md2_log_tile e = g.tiles[lo];
+    const int qpr = (e.w + 3) >> 2;
+    const int q = (b - e.block0) * kBlock + threadIdx.x;
+    const int r = q / qpr, x0 = (q - r * qpr) * 4;
+    if (r >= e.h) return;
+    const int np = min(4, e.w - x0);
+    const int HW = e.h * e.w;
+    uint32_t px[4] = {0u, 0u, 0u, 0u};   // R | G << 8 | B << 16
+    if (e.kind == MD2_LOG_COLOR) {
+        const float* src = (const float*)e.src;
+        for (int i = 0; i < np; ++i) {
+            const int p = r * e.w + x0 + i;
+            px[i] = log_byte(ldf(src, p)) | log_byte(ldf(src, HW + p)) << 8 | log_byte(ldf(src, 2 * HW + p)) << 16;
+        }
+    } else if (e.kind == MD2_LOG_MAP) {
+        const float* src = (const float*)e.src;
+        for (int i = 0; i < np; ++i) px[i] = log_grey(ldf(src, r * e.w + x0 + i));
+    } else if (e.kind == MD2_LOG_DISP) {
+        const float mi = g.stats[2 * (e.item * g.nscales + e.scale) + 0];
+        const float ma = g.stats[2 * (e.item * g.nscales + e.scale) + 1];
+        const float d = (ma != mi) ? (float)((double)ma - (double)mi) : 1e5f;
+        for (int i = 0; i < np; ++i) {
+            const float v = ldd((const float*)e.src, r * e.w + x0 + i, g.p.disp_bf16 != 0);
+            px[i] = log_grey((v - mi) / d);
+        }
+    } else {   // MD2_LOG_WARP: generate_kernel's own sequence for source frame e.frame
+        WarpCtx ctx;
+        make_ctx(g.p, 0, e.frame - 1, e.item, ctx);
+        for (int i = 0; i < np; ++i) {
+            Sample s;
+            project(ctx, r, x0 + i, s);
+            Corners v;
+            gather<false>(ctx, s, v);
+            float o[3];
+            interp<false>(s, v, o);
+            px[i] = log_byte(o[0]) | log_byte(o[1]) << 8 | log_byte(o[2]) << 16;
+        }
+    }
+    uint8_t* row = g.sheet + (((size_t)e.item * g.SH + e.y + r) * g.SW + e.x + x0) * 3;
+    if (((e.w | e.x | g.SW) & 3) == 0) {   // 12 bytes at a 4-byte boundary: three dword stores
+        uint32_t* o = (uint32_t*)row;
+        o[0] = px[0] | px[1] << 24;
+        o[1] = px[1] >> 8 | px[2] << 16;
+        o[2] = px[2] >> 16 | px[3] << 8;
+    } else {
+        for (int i = 0; i < np; ++i) {
+            row[3 * i + 0] = (uint8_t)px[i];
+            row[3 * i + 1] = (uint8_t)(px[i] >> 8);
+            row[3 * i + 2] = (uint8_t)(px[i] >> 16);
+        }
+    }
+}
+
+// ----------------------------------------------------------------------------
 // host side
 // ----------------------------------------------------------------------------
 thread_local char g_err[512] = "";
@@ -2642,6 +2782,154 @@ int md2_timing_calls(double* fwd_ms, int* n_fwd, double* bwd_ms, int* n_bwd) {
     if (bwd_ms) *bwd_ms = g_timing.call_ms[1];
     if (n_bwd) *n_bwd = g_timing.call_n[1];
     return MD2_OK;
+}
+
+// ---- md2_log_panel ----------------------------------------------------------------
+
+int md2_log_panel_tile_blocks(const md2_log_tile* e) {
+    if (!e || e->h < 1 || e->w < 1) return 0;
+    const long long quads = (long long)e->h * ((e->w + 3) / 4);
+    return (int)((quads + kBlock - 1) / kBlock);
+}
+
+static int log_check_desc(const md2_log_desc* d) {
+    if (!d) return fail(MD2_ERR_ARG, "log_panel: NULL desc");
+    const md2_desc& h = d->hot;
+    if (h.batch < 1 || h.height < 1 || h.width < 1)
+        return fail(MD2_ERR_ARG, "log_panel: batch, height and width must be positive (got %d, %d, %d)", h.batch,
+                    h.height, h.width);
+    if (h.num_scales < 1 || h.num_scales > MD2_MAX_SCALES)
+        return fail(MD2_ERR_ARG, "log_panel: num_scales must be 1..%d (got %d)", MD2_MAX_SCALES, h.num_scales);
+    if (h.num_src < 1 || h.num_src > MD2_MAX_SRC)
+        return fail(MD2_ERR_ARG, "log_panel: num_src must be 1..%d (got %d)", MD2_MAX_SRC, h.num_src);
+    if ((h.height >> (h.num_scales - 1)) < 1 || (h.width >> (h.num_scales - 1)) < 1)
+        return fail(MD2_ERR_ARG, "log_panel: scale %d of %d x %d is empty", h.num_scales - 1, h.height, h.width);
+    if ((long long)h.batch * h.height * h.width >= (1ll << 29))
+        return fail(MD2_ERR_ARG, "log_panel: batch * height * width must stay below 2^29");
+    if (h.disp_dtype != MD2_DTYPE_F32 && h.disp_dtype != MD2_DTYPE_BF16)
+        return fail(MD2_ERR_ARG, "log_panel: disp_dtype must be MD2_DTYPE_F32 or MD2_DTYPE_BF16 (got %u)", h.disp_dtype);
+    if (d->items < 1 || d->items > MD2_LOG_MAX_ITEMS || d->items > h.batch)
+        return fail(MD2_ERR_ARG, "log_panel: items must be 1..min(%d, batch = %d) (got %d)", MD2_LOG_MAX_ITEMS, h.batch,
+                    d->items);
+    if (d->sheet_h < 1 || d->sheet_w < 1)
+        return fail(MD2_ERR_ARG, "log_panel: the sheet must be positive (got %d x %d)", d->sheet_h, d->sheet_w);
+    if ((long long)d->items * d->sheet_h * d->sheet_w * 3 >= (1ll << 31))
+        return fail(MD2_ERR_ARG, "log_panel: the sheet must stay below 2^31 bytes");
+    if (d->num_tiles < 1 || d->num_tiles > MD2_LOG_MAX_TILES)
+        return fail(MD2_ERR_ARG, "log_panel: num_tiles must be 1..%d (got %d)", MD2_LOG_MAX_TILES, d->num_tiles);
+    return MD2_OK;
+}
+
+int md2_log_panel_check(const md2_log_desc* d, const md2_log_tile* tiles, const md2_tensors* t) {
+    int rc = log_check_desc(d);
+    if (rc) return rc;
+    if (!tiles) return fail(MD2_ERR_ARG, "log_panel: NULL tile table");
+    const md2_desc& h = d->hot;
+    long long blocks = 0;
+    bool warp = false;
+    for (int i = 0; i < d->num_tiles; ++i) {
+        const md2_log_tile& e = tiles[i];
+        if (e.kind < MD2_LOG_COLOR || e.kind > MD2_LOG_MAP)
+            return fail(MD2_ERR_ARG, "log_panel: tile %d has unknown kind %d", i, e.kind);
+        if (e.item < 0 || e.item >= d->items)
+            return fail(MD2_ERR_ARG, "log_panel: tile %d names item %d of %d", i, e.item, d->items);
+        if (e.scale < 0 || e.scale >= h.num_scales)
+            return fail(MD2_ERR_ARG, "log_panel: tile %d names scale %d of %d", i, e.scale, h.num_scales);
+        if (e.frame < (e.kind == MD2_LOG_WARP ? 1 : 0) || e.frame > h.num_src)
+            return fail(MD2_ERR_ARG, "log_panel: tile %d names frame index %d outside %d..%d", i, e.frame,
+                        e.kind == MD2_LOG_WARP ? 1 : 0, h.num_src);
+        if (e.kind == MD2_LOG_WARP && e.scale != 0)
+            return fail(MD2_ERR_ARG, "log_panel: tile %d is a warp at scale %d (warps are logged at scale 0 only)", i,
+                        e.scale);
+        if (e.kind == MD2_LOG_WARP && (h.height < 2 || h.width < 2))
+            return fail(MD2_ERR_ARG, "log_panel: tile %d is a warp in a frame smaller than 2 x 2", i);
+        const int hs = h.height >> e.scale, ws = h.width >> e.scale;
+        const bool native = e.h == hs && e.w == ws, full = e.h == h.height && e.w == h.width;
+        if (!(native || (e.kind == MD2_LOG_MAP && full)))
+            return fail(MD2_ERR_ARG, "log_panel: tile %d is %d x %d, its kind %d at scale %d needs %d x %d", i, e.h,
+                        e.w, e.kind, e.scale, hs, ws);
+        if (e.y < 0 || e.x < 0 || (long long)e.y + e.h > d->sheet_h || (long long)e.x + e.w > d->sheet_w)
+            return fail(MD2_ERR_ARG, "log_panel: tile %d (%d, %d, %d x %d) leaves the %d x %d sheet", i, e.y, e.x, e.h,
+                        e.w, d->sheet_h, d->sheet_w);
+        if (!e.src) return fail(MD2_ERR_ARG, "log_panel: tile %d has a NULL src", i);
+        if (e.reserved) return fail(MD2_ERR_ARG, "log_panel: tile %d has a non-zero reserved field", i);
+        if (e.block0 != blocks)
+            return fail(MD2_ERR_ARG, "log_panel: tile %d has block0 %d, the running sum is %lld", i, e.block0, blocks);
+        blocks += md2_log_panel_tile_blocks(&e);
+        for (int k = 0; k < i; ++k) {
+            const md2_log_tile& o = tiles[k];
+            if (o.item == e.item && e.y < o.y + o.h && o.y < e.y + e.h && e.x < o.x + o.w && o.x < e.x + e.w)
+                return fail(MD2_ERR_ARG, "log_panel: tiles %d and %d of item %d overlap", k, i, e.item);
+        }
+        warp |= e.kind == MD2_LOG_WARP;
+    }
+    if (blocks >= (1ll << 31)) return fail(MD2_ERR_ARG, "log_panel: too many blocks");
+    if (warp) {
+        if (!t) return fail(MD2_ERR_ARG, "log_panel: a warp tile needs tensors");
+        if (!t->T || !t->disp[0] || !t->K[0] || !t->inv_K[0])
+            return fail(MD2_ERR_ARG, "log_panel: a warp tile needs T, disp[0], K[0] and inv_K[0]");
+        for (int f = 1; f <= h.num_src; ++f)
+            if (!t->color[0][f]) return fail(MD2_ERR_ARG, "log_panel: a warp tile needs color[0][%d]", f);
+        if (!(h.min_depth > 0.f) || !(h.max_depth > h.min_depth))
+            return fail(MD2_ERR_ARG, "log_panel: need 0 < min_depth < max_depth");
+    }
+    return MD2_OK;
+}
+
+size_t md2_log_panel_workspace_bytes(const md2_log_desc* d) {
+    if (log_check_desc(d)) return 0;
+    return align256(sizeof(float) * 2 * (size_t)d->items * d->hot.num_scales);
+}
+
+int md2_log_panel(const md2_log_desc* d, const md2_tensors* t, const md2_log_tile* tiles, int total_blocks,
+                  uint8_t* sheet, void* workspace, void* stream) {
+    int rc = log_check_desc(d);
+    if (rc) return rc;
+    if (!t || !tiles || !sheet || !workspace) return fail(MD2_ERR_ARG, "log_panel: NULL operand");
+    if (((uintptr_t)sheet & 15) || ((uintptr_t)workspace & 255))
+        return fail(MD2_ERR_ARG, "log_panel: the sheet must be 16-byte and the workspace 256-byte aligned");
+    if (total_blocks < 1) return fail(MD2_ERR_ARG, "log_panel: total_blocks must be positive (got %d)", total_blocks);
+    const md2_desc& h = d->hot;
+    for (int s = 0; s < h.num_scales; ++s)
+        if (!t->disp[s]) return fail(MD2_ERR_ARG, "log_panel: disp[%d] is NULL", s);
+    LogArgs g;
+    memset(&g, 0, sizeof(g));
+    PhotoArgs& a = g.p;   // what make_ctx reads for scale 0, as photo_args fills it
+    a.B = h.batch;
+    a.h = h.height;
+    a.w = h.width;
+    a.S = h.num_src;
+    a.nsc = a.num_scales = h.num_scales;
+    for (int f = 0; f < h.num_src; ++f) a.src[f] = t->color[0][f + 1];
+    a.K = t->K[0];
+    a.iK = t->inv_K[0];
+    a.disp_bf16 = h.disp_dtype == MD2_DTYPE_BF16;
+    a.min_disp = 1.0f / h.max_depth;
+    a.range = 1.0f / h.min_depth - 1.0f / h.max_depth;
+    a.flags = h.flags;
+    for (int s = 0; s < h.num_scales; ++s) {
+        a.disp[s] = t->disp[s];
+        a.dh[s] = h.height >> s;
+        a.dw[s] = h.width >> s;
+        a.T[s] = t->T;   // the scale-0 transforms, also with MD2_T_PER_SCALE
+    }
+    g.tiles = tiles;
+    g.ntiles = d->num_tiles;
+    g.items = d->items;
+    g.nscales = h.num_scales;
+    g.SH = d->sheet_h;
+    g.SW = d->sheet_w;
+    g.sheet = sheet;
+    g.stats = (float*)workspace;
+    g.sheet_bytes = (long long)d->items * d->sheet_h * d->sheet_w * 3;
+    hipStream_t st = (hipStream_t)stream;
+    const long long n16 = g.sheet_bytes >> 4;
+    const long long want = (n16 + 4 * kBlock - 1) / (4 * kBlock);   // four stores per thread, up to 8192 blocks
+    const int clear = want < 1 ? 1 : (want > 8192 ? 8192 : (int)want);
+    hipLaunchKernelGGL(log_stats_kernel, dim3(d->items * h.num_scales + clear), dim3(kBlock), 0, st, g);
+    if ((rc = hip_check("log_stats_kernel"))) return rc;
+    hipLaunchKernelGGL(log_panel_kernel, dim3(total_blocks), dim3(kBlock), 0, st, g);
+    return hip_check("log_panel_kernel");
 }
 
 }  // extern "C"

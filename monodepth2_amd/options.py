@@ -88,6 +88,10 @@ _FLAGS = [
     # build-specific
     ("--materialize_images", dict(action="store_true",
                                   help="build: also materialise warped colours/samples/depth every step")),
+    ("--log_images", dict(action="store_true",
+                          help="build: on every log step also write the reference's training pictures (frames, "
+                               "warps, normalised disparities, masks) as PNG contact sheets under "
+                               "<log_dir>/<model_name>/<mode>/images/")),
     ("--noise_seed", dict(type=int, default=0, help="build: seed of the in-kernel tie-break noise")),
     ("--channels_last", dict(type=int, default=1,
                              help="build: 1 (default) NHWC activations/weights for the convolutions, 0 NCHW")),

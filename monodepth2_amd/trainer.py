@@ -11,8 +11,9 @@ Differences from the reference, all deliberate:
   * the tie-break noise of trainer.py:468 is drawn inside the kernel from a
     counter-based generator (seed = noise_seed, step, rank) — no randn launches;
   * `generate_images_pred` materialises warped colours / samples / depth only when
-    asked (logging, evaluation or `--materialize_images`), because the fused loss
-    does not need them;
+    asked (evaluation or `--materialize_images`), because the fused loss does not need
+    them; the log step's pictures (`--log_images`) come from `log_ops.log_panel`, which
+    warps the logged images inside its own kernel;
   * data parallelism: one process per GPU, DDP over RCCL (backend "nccl") with the
     gradient all-reduce bucketed and overlapped with the backward pass.  The
     reference is single-GPU (README.md:147-155).
@@ -31,7 +32,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 import torch.optim as optim
 
-from . import conv_ops, networks
+from . import conv_ops, log_ops, networks
 from .distributed import FlatGradSync, wrap_ddp
 from .eval_ops import depth_metrics
 from .hotpath import HotPathConfig, generate_images, photometric_loss, predictive_mask_inputs, selection_maps
@@ -267,6 +268,7 @@ class Trainer:
             disable_automasking=self.opt.disable_automasking, v1_multiscale=self.opt.v1_multiscale,
             t_per_scale=self.opt.pose_model_type == "posecnn", predictive_mask=bool(self.opt.predictive_mask))
         self.noise_override = None   # {scale: unit-normal noise}; tests pin the tie-break noise with it
+        self._log_plans = {}         # mode -> log_ops.PanelPlan (the sheet and table of the last log step)
         self.depth_metric_names = ["de/abs_rel", "de/sq_rel", "de/rms", "de/log_rms", "da/a1", "da/a2", "da/a3"]
         self.epoch = 0
         self.step = 0
@@ -731,8 +733,14 @@ class Trainer:
                     if self.rank == 0:
                         self.log_time(batch_idx, time.time() - t0, scalars["loss"])
                     self.log_scalars("train", step, scalars)
+                    log_images = bool(getattr(self.opt, "log_images", False))
+                    if log_images:
+                        self.log_images("train", inputs, outputs, step)
                     if val_loader is not None:
-                        self.log_scalars("val", step, self.val(val_loader))
+                        val_scalars, val_inputs, val_outputs = self.val(val_loader, with_tensors=True)
+                        self.log_scalars("val", step, val_scalars)
+                        if log_images:
+                            self.log_images("val", val_inputs, val_outputs, step)
             self.model_lr_scheduler.step()
             self._agree_conv_choices(again=True)
             if (epoch + 1) % self.opt.save_frequency == 0 and self.rank == 0:
@@ -742,8 +750,10 @@ class Trainer:
             self._val_iter.close()   # a loader's iterator owns a producer thread
         self._val_iter = None
 
-    def val(self, val_loader):
-        """trainer.py:211-226: one validation batch, its scalars read back."""
+    def val(self, val_loader, with_tensors: bool = False):
+        """trainer.py:211-226: one validation batch, its scalars read back; with_tensors:
+        (scalars, inputs, outputs), the batch on the device and what the networks and the
+        loss made of it, for log_images."""
         if self._val_iter is None:
             self._val_iter = iter(val_loader)
         try:
@@ -751,18 +761,43 @@ class Trainer:
         except StopIteration:
             self._val_iter = iter(val_loader)
             inputs = next(self._val_iter)
-        _, losses = self.val_step(inputs)
-        return {k: float(v.detach()) for k, v in losses.items() if torch.is_tensor(v) and v.numel() == 1}
+        outputs, losses = self.val_step(inputs)
+        scalars = {k: float(v.detach()) for k, v in losses.items() if torch.is_tensor(v) and v.numel() == 1}
+        return (scalars, inputs, outputs) if with_tensors else scalars
 
     def log_scalars(self, mode: str, step: int, scalars: Dict[str, float]):
         """One JSON object per log step in <log_path>/<mode>/scalars.jsonl (the reference
-        writes tensorboard events, trainer.py:546-551; images are not logged)."""
+        writes tensorboard events, trainer.py:546-551).  The pictures of the same log step
+        are log_images' (--log_images); tensorboard event files are not written."""
         if self.rank != 0:
             return
         folder = os.path.join(self.log_path, mode)
         os.makedirs(folder, exist_ok=True)
         with open(os.path.join(folder, "scalars.jsonl"), "a") as f:
             f.write(json.dumps({"step": step, "epoch": self.epoch, **scalars}) + "\n")
+
+    def log_images(self, mode: str, inputs, outputs, step: Optional[int] = None):
+        """The pictures the reference's log() hands tensorboard (trainer.py:547-572: input
+        frames of every scale, warped sources of scale 0, normalised disparities, the
+        automask or the predictive masks, for the first four images) as one PNG contact
+        sheet per image under <log_path>/<mode>/images/ (log_ops: two launches into a uint8
+        sheet, one copy to the host, which is the only synchronisation).  Built from what
+        the step already holds — the disparities, _stacked_T's transforms, compute_losses'
+        maps: nothing is materialised, generate_images_pred does not run.  `outputs` of a
+        replayed hipGraph are its static tensors, read here in stream order behind the
+        replay and before the next one.  Rank 0 only.  Returns the panel (None elsewhere)."""
+        if self.rank != 0:
+            return None
+        if self.use_graph and mode == "train" and self.graph is not None:
+            inputs = self.static_inputs   # the batch as the replay saw it, on the device
+        with torch.no_grad():
+            T = self._stacked_T(inputs, outputs).detach()
+            panel = log_ops.log_panel(self.hot, inputs, outputs, self.opt.frame_ids, T,
+                                      plan=self._log_plans.get(mode))
+        self._log_plans[mode] = panel.plan
+        log_ops.write_panel(panel, os.path.join(self.log_path, mode, "images"),
+                            self.step if step is None else step)
+        return panel
 
     def val_step(self, inputs):
         """One validation batch (trainer.py:211-226 val()): the networks in eval mode under
