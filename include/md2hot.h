@@ -1122,6 +1122,68 @@ size_t md2_log_panel_workspace_bytes(const md2_log_desc* desc);
 int md2_log_panel(const md2_log_desc* desc, const md2_tensors* tensors, const md2_log_tile* tiles,
                   int total_blocks, uint8_t* sheet, void* workspace, void* stream);
 
+/*
+ * Depth maps -> point cloud (csrc/points.hip): the reference's disp_to_depth
+ * (layers.py:16-25) and BackprojectDepth (layers.py:139-168) per pixel in fp32, for a batch
+ * of equally sized maps at the original image size, with the pixels that are invalid or
+ * out of range dropped, the survivors compacted in (image, row, column) order over the whole
+ * batch and packed as the 15-byte vertex records of a binary little-endian PLY file: the
+ * first 15 * offsets[B] bytes of `vertices` are the file's body.  Three launches on
+ * `stream` (count per block, scan of the block counts, emit).  New symbols under ABI 24, no
+ * version bump (as md2_disp_colorize).
+ *
+ * map: fp32 (B, H, W); rgb: uint8 (B, H, W, 3); inv_K: fp32 (B, 4, 4) row-major, only rows
+ * and columns 0..2 are read; T: fp32 (B, 4, 4), rows 0..2 are read, required with
+ * MD2_POINTS_WORLD and NULL without it; vertices: `capacity` records of 15 bytes, any
+ * alignment; offsets: uint32 [B + 1].  All on the device.  Per pixel (b, y, x) with d the
+ * map's value, every product and sum one fp32 operation in this order (no contraction):
+ *   1. sd = disp_b + disp_a * d
+ *   2. depth = 1.0f / sd; with MD2_POINTS_DEPTH_INPUT depth = d (disp_a, disp_b ignored)
+ *   3. z = depth_scale * depth
+ *   4. r_i = (k[i][0] * (float)x + k[i][1] * (float)y) + k[i][2], i = 0..2, k = inv_K[b]; x
+ *      and y are the integer pixel indices (no half-pixel offset, the reference's meshgrid)
+ *   5. P_i = z * r_i
+ *   6. with MD2_POINTS_WORLD: Q_i = ((t[i][0]*P_0 + t[i][1]*P_1) + t[i][2]*P_2) + t[i][3],
+ *      t = T[b], and the record holds Q, else P.
+ * A pixel is kept when y % stride == 0 and x % stride == 0, near <= z <= far (both ends
+ * inclusive, z in the camera frame, before T) and the three stored coordinates are finite;
+ * a NaN fails the comparisons by itself.  A record: x, y, z as little-endian float32, then
+ * red, green, blue (the pixel's bytes).  offsets[0] = 0, offsets[b + 1] = the records of
+ * images 0..b.  Exactly bytes 0 .. 15 * offsets[B] of `vertices` are written, each once; no
+ * byte after them is touched.
+ * No atomics, a record's slot comes from the scan: the order is fixed and the output
+ * bitwise repeatable.  hipGraph-capturable, no allocation, no host synchronisation.
+ * Refused (MD2_ERR_ARG) before any launch: a NULL desc, map, rgb, inv_K, vertices, offsets
+ * or workspace; T without MD2_POINTS_WORLD or the flag without T; a non-positive batch,
+ * height, width or stride; batch > 65535; batch * ceil(height / stride) * ceil(width /
+ * stride) >= 2^31; capacity below that product (so no record can land outside `vertices`
+ * whatever the map holds); near or far not finite, near <= 0 or near > far (a sparse map's
+ * zeros are never points); a depth_scale that is not positive and finite; unknown flag bits
+ * or non-zero reserved words; a workspace not 256-byte aligned.  What cannot be checked:
+ * that map, rgb, inv_K, T, vertices, offsets and the workspace are as large as the desc
+ * and `capacity` say.
+ * workspace: the size the query returns (one word per block), no initialisation needed.
+ */
+#define MD2_POINTS_DEPTH_INPUT (1u << 0)   /* the map holds depth, not the network's disparity */
+#define MD2_POINTS_WORLD (1u << 1)         /* apply T: records in the world frame */
+
+typedef struct md2_points_desc {
+    int32_t batch;                  /* B images, 1..65535 */
+    int32_t height, width;          /* of map and rgb */
+    int32_t stride;                 /* every stride-th row and column; 1: every pixel */
+    float disp_a, disp_b;           /* f32(1/min_depth - 1/max_depth), f32(1/max_depth) (offset 16) */
+    float depth_scale;              /* 1, or the reference's STEREO_SCALE_FACTOR (offset 24) */
+    float near, far;                /* the kept range of z, inclusive (offset 28) */
+    uint32_t flags;                 /* MD2_POINTS_* (offset 36) */
+    uint32_t reserved[2];           /* 0; the struct is 48 bytes */
+} md2_points_desc;
+
+/* 0 (and md2_last_error) for a desc md2_depth_points would refuse */
+size_t md2_depth_points_workspace_bytes(const md2_points_desc* desc);
+int md2_depth_points(const md2_points_desc* desc, const float* map, const uint8_t* rgb, const float* inv_K,
+                     const float* T, uint8_t* vertices, size_t capacity, uint32_t* offsets, void* workspace,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -80,7 +80,8 @@ EXPORTS = ["md2_abi_version", "md2_last_error", "md2_workspace_bytes", "md2_sele
            "md2_depth_export16", "md2_depth_export16_check",
            "md2_jpeg_workspace_bytes", "md2_jpeg_check", "md2_jpeg_plan_create", "md2_jpeg_plan_destroy",
            "md2_jpeg_run",
-           "md2_log_panel_tile_blocks", "md2_log_panel_check", "md2_log_panel_workspace_bytes", "md2_log_panel"]
+           "md2_log_panel_tile_blocks", "md2_log_panel_check", "md2_log_panel_workspace_bytes", "md2_log_panel",
+           "md2_depth_points", "md2_depth_points_workspace_bytes"]
 
 DTYPE_F32 = 0    # md2_desc.disp_dtype
 DTYPE_BF16 = 1
@@ -266,7 +267,24 @@ class LogDesc(ctypes.Structure):
                 ("num_tiles", ctypes.c_int32)]
 
 
+# md2_depth_points (csrc/points.hip): new symbols under ABI 24, no version bump
+POINTS_DEPTH_INPUT = 1 << 0
+POINTS_WORLD = 1 << 1
+POINTS_RECORD_BYTES = 15
+
+
+class PointsDesc(ctypes.Structure):
+    _fields_ = [("batch", ctypes.c_int32), ("height", ctypes.c_int32), ("width", ctypes.c_int32),
+                ("stride", ctypes.c_int32), ("disp_a", ctypes.c_float), ("disp_b", ctypes.c_float),
+                ("depth_scale", ctypes.c_float), ("near", ctypes.c_float), ("far", ctypes.c_float),
+                ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 2)]
+
+
 def _declare(L):
+    L.md2_depth_points_workspace_bytes.restype = ctypes.c_size_t
+    L.md2_depth_points_workspace_bytes.argtypes = [ctypes.POINTER(PointsDesc)]
+    L.md2_depth_points.restype = ctypes.c_int
+    L.md2_depth_points.argtypes = [ctypes.POINTER(PointsDesc)] + [_vp] * 5 + [ctypes.c_size_t] + [_vp] * 3
     L.md2_log_panel_tile_blocks.restype = ctypes.c_int
     L.md2_log_panel_tile_blocks.argtypes = [ctypes.POINTER(LogTile)]
     L.md2_log_panel_check.restype = ctypes.c_int

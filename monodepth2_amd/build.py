@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB_NAME = "libmd2hot.so"
 LIB_PATH = os.path.join(CSRC, LIB_NAME)
-SOURCES = ["md2hot.hip", "decoder.hip", "pose.hip", "augment.hip", "bnorm.hip", "pool.hip", "adam.hip", "disphead.hip", "stem.hip", "bias_act.hip", "conv.hip", "direct.hip", "glue.hip", "eval.hip", "velo.hip", "traj.hip", "viz.hip", "jpeg.hip"]
+SOURCES = ["md2hot.hip", "decoder.hip", "pose.hip", "augment.hip", "bnorm.hip", "pool.hip", "adam.hip", "disphead.hip", "stem.hip", "bias_act.hip", "conv.hip", "direct.hip", "glue.hip", "eval.hip", "velo.hip", "traj.hip", "viz.hip", "jpeg.hip", "points.hip"]
 HEADERS = [os.path.join(INCLUDE, "md2hot.h"), os.path.join(CSRC, "md2_bf16.h"), os.path.join(CSRC, "md2_bn_expr.h"),
            os.path.join(CSRC, "md2_x6.h")]
 ARCH = os.environ.get("MD2_OFFLOAD_ARCH", "gfx950")
@@ -79,6 +79,8 @@ BUILD_ID_MARKER = b"md2-build-id:"
 # (three alternated runs each, pinned convolution choices; iterative-ilp equal to the
 # default there); bnorm.hip + decoder.hip with it too: 11.721 -> 11.693 ms (three
 # alternated pairs, every pair faster); stem.hip and direct.hip were slower with it.
+# points.hip: no SLP either — the camera products became v_pk_mul_f32 with that src1
+# op_sel encoding, and its outputs must be bit-equal to the numpy restatement.
 # jpeg.hip with wrapping signed arithmetic: the inverse DCT of a corrupt stream's
 # coefficients can pass 32 bits, and what it gives then must be defined (and unused).
 FLAGS = {"md2hot.hip": ["-fno-slp-vectorize", "-mllvm", "--amdgpu-sched-strategy=iterative-ilp"],
@@ -86,6 +88,7 @@ FLAGS = {"md2hot.hip": ["-fno-slp-vectorize", "-mllvm", "--amdgpu-sched-strategy
          "bnorm.hip": ["-mllvm", "--amdgpu-sched-strategy=max-ilp"],
          "decoder.hip": ["-mllvm", "--amdgpu-sched-strategy=max-ilp"],
          "disphead.hip": ["-fno-slp-vectorize"], "glue.hip": ["-fno-slp-vectorize"],
+         "points.hip": ["-fno-slp-vectorize"],
          "jpeg.hip": ["-fwrapv"]}
 
 
