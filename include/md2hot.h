@@ -1008,6 +1008,7 @@ int md2_depth_export16(const md2_depth16_desc* desc, const float* disp, const fl
 #define MD2_JPEG_ST_BLOCKS (1u << 0)   /* the stream holds fewer or more blocks than the image */
 #define MD2_JPEG_ST_CODE   (1u << 1)   /* a bit pattern that is no Huffman code */
 #define MD2_JPEG_ST_END    (1u << 2)   /* a symbol reaches past the end of the stream */
+#define MD2_JPEG_ST_INDEX  (1u << 3)   /* md2_jpeg_run_indexed: the index does not fit the stream */
 
 typedef struct md2_jpeg_image {
     uint64_t stream_offset;         /* bytes into streams, a multiple of 4 */
@@ -1039,6 +1040,55 @@ md2_jpeg_plan* md2_jpeg_plan_create(int max_images, size_t workspace_bytes);
 void md2_jpeg_plan_destroy(md2_jpeg_plan* plan);
 int md2_jpeg_run(md2_jpeg_plan* plan, const uint8_t* streams, uint64_t streams_bytes, const md2_jpeg_image* images,
                  int n, const md2_jpeg_bank* bank, uint8_t* out, uint64_t out_bytes, uint32_t* status, void* stream);
+
+/*
+ * Decoding from a stored synchronisation index (csrc/jpeg.hip; monodepth2_amd/pack.py keeps
+ * the index beside each stream).  The entry states md2_jpeg_run's entropy kernel finds by
+ * fixed-point iteration are a property of the file, so they are computed once
+ * (md2_jpeg_index) and every later decode (md2_jpeg_run_indexed) starts each 1024-bit
+ * subsequence of every image from its stored state, one thread per subsequence, workgroups
+ * over (image, group of subsequences): no rounds, no barrier after the Huffman tables are
+ * built, the whole batch spread over the GPU.  New symbols under ABI 24, no version bump
+ * (as md2_jpeg_run).
+ *
+ * An image's index, for nsub = max(ceil(8 * stream_bytes / 1024), 1) subsequences: nsub
+ * uint64 entry states (bit << 16 | block_in_mcu << 8 | zigzag: the decoder's state at the
+ * first symbol that starts at or after bit 1024 i), then nsub uint32 first_block values
+ * (the blocks completed before that state), zero padded to a multiple of 16 bytes:
+ * md2_jpeg_index_bytes(stream_bytes), 12 bytes per 128 stream bytes.  md2_jpeg_image stays as
+ * it is; where each image's index lies travels as a parallel HOST array index_offsets[n]
+ * (multiples of 16).
+ *
+ * md2_jpeg_index: images, streams, bank, status and plan as for md2_jpeg_run (out_offset is
+ * not used; the plan needs md2_jpeg_workspace_bytes of the batch); runs the synchronisation
+ * alone, writes no frame, and writes image i's index at index + index_offsets[i] (`index`: DEVICE
+ * bytes, 16-byte aligned, index_bytes long).  status: 0, or MD2_JPEG_ST_BLOCKS when the
+ * stream does not hold exactly the image's blocks.
+ *
+ * md2_jpeg_run_indexed: as md2_jpeg_run, with image i's index read from streams +
+ * index_offsets[i] (streams 16-byte aligned).  The chain is memset, the indexed entropy
+ * kernel, then md2_jpeg_run's DC scan, inverse DCT and colour kernels; with its true index a
+ * stream that holds exactly its image's blocks gives md2_jpeg_run's bytes and status 0 (one
+ * that does not reports MD2_JPEG_ST_INDEX beside md2_jpeg_run's bits: a short stream and a
+ * wrong last count cannot be told apart).  The index is not trusted: every
+ * subsequence checks its entry state's range, its exit state against the next entry and its
+ * block count against the next first_block (the last against the image's blocks); a
+ * mismatch sets MD2_JPEG_ST_INDEX in the image's status word, the frame is then unspecified
+ * and the other frames of the batch are unaffected.  Whatever the index says, reads stay
+ * inside streams and writes inside the image's own coefficient planes.  Refused
+ * (MD2_ERR_ARG) before anything is launched: what md2_jpeg_run refuses, NULL index_offsets,
+ * an index offset that is no multiple of 16, an index that leaves streams_bytes.
+ * md2_jpeg_check_indexed runs those checks alone.
+ */
+size_t md2_jpeg_index_bytes(uint32_t stream_bytes);
+int md2_jpeg_index(md2_jpeg_plan* plan, const uint8_t* streams, uint64_t streams_bytes, const md2_jpeg_image* images,
+                   const uint64_t* index_offsets, int n, const md2_jpeg_bank* bank, uint8_t* index,
+                   uint64_t index_bytes, uint32_t* status, void* stream);
+int md2_jpeg_check_indexed(const md2_jpeg_image* images, const uint64_t* index_offsets, int n, int num_quant,
+                           int num_huff, uint64_t streams_bytes, uint64_t out_bytes);
+int md2_jpeg_run_indexed(md2_jpeg_plan* plan, const uint8_t* streams, uint64_t streams_bytes,
+                         const md2_jpeg_image* images, const uint64_t* index_offsets, int n,
+                         const md2_jpeg_bank* bank, uint8_t* out, uint64_t out_bytes, uint32_t* status, void* stream);
 
 /*
  * The training log's pictures (csrc/md2hot.hip): what the reference's Trainer.log writes at

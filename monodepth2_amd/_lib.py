@@ -80,6 +80,7 @@ EXPORTS = ["md2_abi_version", "md2_last_error", "md2_workspace_bytes", "md2_sele
            "md2_depth_export16", "md2_depth_export16_check",
            "md2_jpeg_workspace_bytes", "md2_jpeg_check", "md2_jpeg_plan_create", "md2_jpeg_plan_destroy",
            "md2_jpeg_run",
+           "md2_jpeg_index_bytes", "md2_jpeg_index", "md2_jpeg_check_indexed", "md2_jpeg_run_indexed",
            "md2_log_panel_tile_blocks", "md2_log_panel_check", "md2_log_panel_workspace_bytes", "md2_log_panel",
            "md2_depth_points", "md2_depth_points_workspace_bytes"]
 
@@ -235,6 +236,7 @@ class Depth16Desc(ctypes.Structure):
 # md2_jpeg_run (csrc/jpeg.hip): new symbols under ABI 24, no version bump
 JPEG_444, JPEG_422, JPEG_420 = 0, 1, 2
 JPEG_ST_BLOCKS, JPEG_ST_CODE, JPEG_ST_END = 1, 2, 4
+JPEG_ST_INDEX = 8        # md2_jpeg_run_indexed: the stored index does not fit the stream
 JPEG_QUANT_BYTES = 128   # one bank.quant table: 64 uint16, natural order
 JPEG_HUFF_BYTES = 272    # one bank.huff table: counts[16], values[256]
 
@@ -305,6 +307,18 @@ def _declare(L):
     L.md2_jpeg_run.restype = ctypes.c_int
     L.md2_jpeg_run.argtypes = [_vp, _vp, ctypes.c_uint64, ctypes.POINTER(JpegImage), ctypes.c_int,
                                ctypes.POINTER(JpegBank), _vp, ctypes.c_uint64, _vp, _vp]
+    L.md2_jpeg_index_bytes.restype = ctypes.c_size_t
+    L.md2_jpeg_index_bytes.argtypes = [ctypes.c_uint32]
+    L.md2_jpeg_index.restype = ctypes.c_int
+    L.md2_jpeg_index.argtypes = [_vp, _vp, ctypes.c_uint64, ctypes.POINTER(JpegImage), ctypes.POINTER(ctypes.c_uint64),
+                                 ctypes.c_int, ctypes.POINTER(JpegBank), _vp, ctypes.c_uint64, _vp, _vp]
+    L.md2_jpeg_check_indexed.restype = ctypes.c_int
+    L.md2_jpeg_check_indexed.argtypes = [ctypes.POINTER(JpegImage), ctypes.POINTER(ctypes.c_uint64), ctypes.c_int,
+                                         ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64]
+    L.md2_jpeg_run_indexed.restype = ctypes.c_int
+    L.md2_jpeg_run_indexed.argtypes = [_vp, _vp, ctypes.c_uint64, ctypes.POINTER(JpegImage),
+                                       ctypes.POINTER(ctypes.c_uint64), ctypes.c_int, ctypes.POINTER(JpegBank), _vp,
+                                       ctypes.c_uint64, _vp, _vp]
     L.md2_depth_export16.restype = ctypes.c_int
     L.md2_depth_export16.argtypes = [ctypes.POINTER(Depth16Desc)] + [_vp] * 4
     L.md2_depth_export16_check.restype = ctypes.c_int

@@ -35,6 +35,12 @@
 // index past 63 ends the block, coefficient writes happen only in the final pass and only
 // for blocks below the image's block count, and every loop advances the bit position.
 //
+// The slots the iteration ends with are a property of the file.  md2_jpeg_index runs the
+// iteration alone and writes them out with the blocks completed before each (the index);
+// md2_jpeg_run_indexed replaces `entropy` by jpeg_entropy_indexed_kernel, which starts every
+// subsequence of every image from its stored slot: workgroups over (image, group of
+// subsequences), no rounds, and every exit state checked against the next stored one.
+//
 // Integer arithmetic only; no atomics on coefficients, samples or pixels (the status word
 // takes an atomic OR).  Products that a corrupt stream can push past 32 bits wrap (-fwrapv).
 
@@ -52,6 +58,7 @@ int md2_report_error(int code, const char* msg);
 namespace {
 
 constexpr int kThreads = 1024;        // entropy and dc workgroups
+constexpr int kIxThreads = 256;       // indexed entropy workgroups
 constexpr int kSubBits = 1024;        // bits per subsequence (128 bytes)
 constexpr int kFastBits = 9;          // Huffman codes up to this length: one LDS lookup
 constexpr int kRing = 4;              // pinned descriptor slots per plan
@@ -63,6 +70,7 @@ constexpr int kHuffBytes = 272;       // counts[16], values[256]
 constexpr uint32_t kStShort = MD2_JPEG_ST_BLOCKS;
 constexpr uint32_t kStCode = MD2_JPEG_ST_CODE;
 constexpr uint32_t kStEnd = MD2_JPEG_ST_END;
+constexpr uint32_t kStIndex = MD2_JPEG_ST_INDEX;
 
 __device__ const unsigned char kZigzag[64] = {
     0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
@@ -86,6 +94,8 @@ struct Img {                  // one image of the batch, on the device
     uint32_t nsub;
     uint8_t* out;
     uint32_t* status;
+    unsigned long long* ix_state;   // md2_jpeg_index / md2_jpeg_run_indexed: nsub entry states
+    uint32_t* ix_first;             // and nsub counts of the blocks completed before them
 };
 
 struct Huff {                 // one table in LDS
@@ -240,10 +250,12 @@ __device__ uint32_t decode_range(const Img& im, const Huff* tabs, Bits& bits, un
     return done;
 }
 
-// LDS tables of the image's six (component, DC / AC) pairs from the bank's counts and values
+// LDS tables of the image's six (component, DC / AC) pairs from the bank's counts and values,
+// by a workgroup of STRIDE threads (at least 6)
+template <int STRIDE>
 __device__ void build_tables(const Img& im, const uint8_t* huff, int num_huff, Huff* tabs) {
     const int t = threadIdx.x;
-    for (int i = t; i < 6 * (1 << kFastBits); i += kThreads) tabs[i >> kFastBits].fast[i & ((1 << kFastBits) - 1)] = 0;
+    for (int i = t; i < 6 * (1 << kFastBits); i += STRIDE) tabs[i >> kFastBits].fast[i & ((1 << kFastBits) - 1)] = 0;
     if (t < 6) {
         int id = (t & 1) ? im.act[t >> 1] : im.dct[t >> 1];
         id = id < 0 ? 0 : (id >= num_huff ? num_huff - 1 : id);
@@ -261,14 +273,14 @@ __device__ void build_tables(const Img& im, const uint8_t* huff, int num_huff, H
         H.maxcode[0] = -1;
         H.base[0] = 0;
     }
-    for (int i = t; i < 6 * 256; i += kThreads) {
+    for (int i = t; i < 6 * 256; i += STRIDE) {
         const int id0 = ((i >> 8) & 1) ? im.act[i >> 9] : im.dct[i >> 9];
         const int id = id0 < 0 ? 0 : (id0 >= num_huff ? num_huff - 1 : id0);
         tabs[i >> 8].vals[i & 255] = huff[(size_t)id * kHuffBytes + 16 + (i & 255)];
     }
     __syncthreads();
     // symbol j of table q: its length and code, then every lookup entry it prefixes
-    for (int i = t; i < 6 * 256; i += kThreads) {
+    for (int i = t; i < 6 * 256; i += STRIDE) {
         const int q = i >> 8, j = i & 255;
         const int id0 = (q & 1) ? im.act[q >> 1] : im.dct[q >> 1];
         const int id = id0 < 0 ? 0 : (id0 >= num_huff ? num_huff - 1 : id0);
@@ -309,13 +321,15 @@ __device__ uint32_t block_scan(uint32_t v, uint32_t* lds, uint32_t* total) {
     return incl - v;
 }
 
-// grid: images
+// grid: images.  INDEX: the synchronisation alone; the final slots and the blocks before each
+// go to the image's index and nothing is decoded for real (md2_jpeg_index).
+template <bool INDEX>
 __global__ __launch_bounds__(kThreads) void jpeg_entropy_kernel(const Img* imgs, const uint8_t* huff, int num_huff) {
     __shared__ Huff tabs[6];
     __shared__ uint32_t scan[kThreads];
     const Img& im = imgs[blockIdx.x];
     const int t = threadIdx.x;
-    build_tables(im, huff, num_huff, tabs);
+    build_tables<kThreads>(im, huff, num_huff, tabs);
     for (uint32_t i = t; i <= im.nsub; i += kThreads) {
         slot_store(&im.slots[i], pack_state(i * (uint32_t)kSubBits, 0, 0));
         im.dirty[i] = 0;
@@ -349,6 +363,17 @@ __global__ __launch_bounds__(kThreads) void jpeg_entropy_kernel(const Img* imgs,
     for (uint32_t i = first; i < last; ++i) mine += im.counts[i];
     uint32_t total;
     uint32_t g = block_scan(mine, scan, &total);
+    if (INDEX) {
+        for (uint32_t i = first; i < last; ++i) {
+            im.ix_state[i] = slot_load(&im.slots[i]);
+            im.ix_first[i] = g;
+            g += im.counts[i];
+        }
+        // the index is padded to 16 bytes: 12 * nsub bytes, then (nsub & 3) words of zeros
+        if ((uint32_t)t < (im.nsub & 3u)) im.ix_first[im.nsub + t] = 0;
+        if (t == 0 && total != im.total_blocks) atomicOr(im.status, kStShort);
+        return;
+    }
     for (uint32_t i = first; i < last; ++i) {
         unsigned long long st = slot_load(&im.slots[i]);
         const uint32_t n = im.counts[i];
@@ -356,6 +381,59 @@ __global__ __launch_bounds__(kThreads) void jpeg_entropy_kernel(const Img* imgs,
         g += n;
     }
     if (t == 0 && total != im.total_blocks) flags |= kStShort;
+    if (flags) atomicOr(im.status, flags);
+}
+
+// grid (ceil(max nsub / kIxThreads), images): the entropy decode from a stored index
+// (md2_jpeg_run_indexed).  A workgroup belongs to one image and builds its tables; thread t
+// then decodes subsequence i = blockIdx.x * kIxThreads + t from ix_state[i] with ix_first[i]
+// blocks before it, independently of every other: no barrier after the table build, no slot
+// memory, no atomic but the status word's (cleared by a memset before the launch, since
+// several workgroups share it).  One subsequence per thread: a KITTI batch has about one
+// wave per SIMD of them, and two or four per thread measured 1.24 and 1.89 times the chain's
+// time.
+//
+// The index is not trusted.  An entry state must be 0 for subsequence 0 and otherwise hold a
+// bit position in [kSubBits * i, stream bits]: anything else is reported and not decoded, so
+// a thread never decodes more than its kSubBits bits.  After the decode, with g1 = ix_first[i]
+// + blocks completed: while g1 is below the image's block count, the exit state must equal
+// ix_state[i + 1] and g1 must equal ix_first[i + 1]; once the image's blocks are complete
+// (the decode stops there, the synchronisation that made the index did not, so their states
+// may differ) ix_first[i + 1] must not be below the block count either; the last subsequence
+// must end at exactly the block count.  A mismatch sets MD2_JPEG_ST_INDEX (with _BLOCKS for
+// the last subsequence).  Writes are clamped to the image's own planes by block_ptr and
+// decode_range whatever the index says.
+__global__ __launch_bounds__(kIxThreads) void jpeg_entropy_indexed_kernel(const Img* imgs, const uint8_t* huff,
+                                                                          int num_huff) {
+    __shared__ Huff tabs[6];
+    const Img& im = imgs[blockIdx.y];
+    if (blockIdx.x * (uint32_t)kIxThreads >= im.nsub) return;   // the whole workgroup: the grid is the largest image's
+    build_tables<kIxThreads>(im, huff, num_huff, tabs);
+    const uint32_t i = blockIdx.x * (uint32_t)kIxThreads + threadIdx.x;
+    if (i >= im.nsub) return;
+    Bits bits;
+    bits.init(im);
+    const uint32_t total_bits = im.nbytes * 8u;
+    unsigned long long st = im.ix_state[i];
+    const uint32_t g0 = im.ix_first[i];
+    const uint32_t p = (uint32_t)(st >> 16);
+    if ((st >> 48) || p < i * (uint32_t)kSubBits || p > total_bits || (i == 0 && (st || g0))) {
+        atomicOr(im.status, kStIndex);
+        return;
+    }
+    uint32_t flags = 0, done = 0;
+    if (g0 < im.total_blocks) done = decode_range<true>(im, tabs, bits, st, (i + 1) * (uint32_t)kSubBits, g0, flags);
+    const uint32_t g1 = g0 + done;
+    if (i + 1 == im.nsub) {
+        if (g1 != im.total_blocks) flags |= kStIndex | kStShort;
+    } else {
+        const uint32_t next = im.ix_first[i + 1];
+        if (g1 < im.total_blocks) {
+            if (st != im.ix_state[i + 1] || g1 != next) flags |= kStIndex;
+        } else if (next < im.total_blocks) {
+            flags |= kStIndex;
+        }
+    }
     if (flags) atomicOr(im.status, flags);
 }
 
@@ -548,6 +626,14 @@ const char* check_image(const md2_jpeg_image& im) {
     return nullptr;
 }
 
+uint32_t stream_nsub(const md2_jpeg_image& im) {
+    const uint32_t nsub = (uint32_t)(((uint64_t)im.stream_bytes * 8 + kSubBits - 1) / kSubBits);
+    return nsub ? nsub : 1;
+}
+
+// an image's index: nsub 64-bit entry states, nsub 32-bit block counts, padded to 16 bytes
+size_t index_size(uint32_t nsub) { return ((size_t)nsub * 12 + 15) & ~(size_t)15; }
+
 Geometry geometry(const md2_jpeg_image& im) {
     Geometry g;
     g.hs = im.sampling == MD2_JPEG_444 ? 1 : 2;
@@ -561,8 +647,7 @@ Geometry geometry(const md2_jpeg_image& im) {
         g.blocks[c] = (size_t)g.wb[c] * g.hb[c];
     }
     g.total_blocks = (size_t)g.mcux * g.mcuy * g.bpm;
-    g.nsub = (uint32_t)(((uint64_t)im.stream_bytes * 8 + kSubBits - 1) / kSubBits);
-    if (g.nsub == 0) g.nsub = 1;
+    g.nsub = stream_nsub(im);
     return g;
 }
 
@@ -597,7 +682,7 @@ Layout layout(const md2_jpeg_image* images, int n) {
 }
 
 const char* check_ranges(const md2_jpeg_image* images, int n, int num_quant, int num_huff, uint64_t streams_bytes,
-                         uint64_t out_bytes) {
+                         uint64_t out_bytes, bool frames) {
     if (num_quant < 1 || num_huff < 1 || num_quant > 256 || num_huff > 256)
         return "jpeg: the bank needs 1..256 quantisation and 1..256 Huffman tables";
     for (int i = 0; i < n; ++i) {
@@ -609,7 +694,19 @@ const char* check_ranges(const md2_jpeg_image* images, int n, int num_quant, int
         if (im.stream_offset > streams_bytes || sb > streams_bytes - im.stream_offset)
             return "jpeg: a stream reaches past streams_bytes";
         const uint64_t ob = (uint64_t)im.height * im.width * 3;
-        if (im.out_offset > out_bytes || ob > out_bytes - im.out_offset) return "jpeg: a frame reaches past out_bytes";
+        if (frames && (im.out_offset > out_bytes || ob > out_bytes - im.out_offset))
+            return "jpeg: a frame reaches past out_bytes";
+    }
+    return nullptr;
+}
+
+// every image's index lies, 16-byte aligned, inside a buffer of `bytes` bytes (`past`: what to say if not)
+const char* check_index(const md2_jpeg_image* images, const uint64_t* index_offsets, int n, uint64_t bytes,
+                        const char* past) {
+    for (int i = 0; i < n; ++i) {
+        if (index_offsets[i] % 16) return "jpeg: an index offset must be a multiple of 16";
+        const uint64_t ib = index_size(stream_nsub(images[i]));
+        if (index_offsets[i] > bytes || ib > bytes - index_offsets[i]) return past;
     }
     return nullptr;
 }
@@ -626,6 +723,102 @@ struct md2_jpeg_plan {
     int slot = 0;
 };
 
+// The launches of md2_jpeg_run (kRun), md2_jpeg_run_indexed (kRunIndexed: index_base is the
+// streams buffer) and md2_jpeg_index (kIndex: index_base is the index buffer, out is NULL)
+// for a batch that has passed their checks.
+enum Mode { kRun, kRunIndexed, kIndex };
+
+static int run_chain(Mode mode, md2_jpeg_plan* P, const uint8_t* streams, const md2_jpeg_image* images,
+                     const uint64_t* index_offsets, int n, const md2_jpeg_bank* bank, uint8_t* out,
+                     uint8_t* index_base, uint32_t* status, void* stream) {
+    if (reinterpret_cast<uintptr_t>(streams) % 4)
+        return md2_report_error(MD2_ERR_ARG, "jpeg: streams must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(bank->quant) % 16)
+        return md2_report_error(MD2_ERR_ARG, "jpeg: bank.quant must be 16-byte aligned");
+    if (n > P->max_images) return md2_report_error(MD2_ERR_ARG, "jpeg: more images than the plan was created for");
+    const Layout l = layout(images, n);
+    if (l.total > P->workspace_bytes)
+        return md2_report_error(MD2_ERR_ARG, "jpeg: the batch needs more workspace than the plan owns");
+
+    hipStream_t st = (hipStream_t)stream;
+    const int r = P->slot;
+    P->slot = (P->slot + 1) % kRing;
+    if (hipEventSynchronize(P->staged[r]) != hipSuccess)
+        return md2_report_error(MD2_ERR_HIP, "jpeg: waiting for a staging slot failed");
+    Img* host = P->host_imgs + (size_t)r * P->max_images;
+    Img* dev = P->dev_imgs + (size_t)r * P->max_images;
+    size_t o_coef = 0, o_rest = l.coef_bytes, max_blocks = 0, max_pixels = 0;
+    uint32_t max_nsub = 1;
+    for (int i = 0; i < n; ++i) {
+        const md2_jpeg_image& im = images[i];
+        const Geometry g = geometry(im);
+        Img& d = host[i];
+        memset(&d, 0, sizeof(d));
+        d.words = reinterpret_cast<const uint32_t*>(streams + im.stream_offset);
+        d.nbytes = im.stream_bytes;
+        d.h = im.height; d.w = im.width; d.hs = g.hs; d.vs = g.vs;
+        d.mcux = g.mcux; d.mcuy = g.mcuy; d.bpm = g.bpm;
+        d.total_blocks = (uint32_t)g.total_blocks;
+        size_t oc = o_coef, op = o_rest;
+        for (int c = 0; c < 3; ++c) {
+            d.qt[c] = im.quant[c]; d.dct[c] = im.dc[c]; d.act[c] = im.ac[c];
+            d.wb[c] = g.wb[c]; d.hb[c] = g.hb[c];
+            d.coef[c] = reinterpret_cast<int16_t*>(P->workspace + oc);
+            d.plane[c] = reinterpret_cast<uint8_t*>(P->workspace + op);
+            oc += g.blocks[c] * 64 * sizeof(int16_t);
+            op += g.blocks[c] * 64;
+            if (g.blocks[c] > max_blocks) max_blocks = g.blocks[c];
+        }
+        o_coef += align256(g.total_blocks * 64 * sizeof(int16_t));
+        o_rest += align256(g.total_blocks * 64);
+        d.slots = reinterpret_cast<unsigned long long*>(P->workspace + o_rest);
+        o_rest += align256(((size_t)g.nsub + 1) * sizeof(unsigned long long));
+        d.dirty = reinterpret_cast<uint32_t*>(P->workspace + o_rest);
+        o_rest += align256(((size_t)g.nsub + 1) * sizeof(uint32_t));
+        d.counts = reinterpret_cast<uint32_t*>(P->workspace + o_rest);
+        o_rest += align256((size_t)g.nsub * sizeof(uint32_t));
+        d.nsub = g.nsub;
+        d.out = out ? out + im.out_offset : nullptr;
+        if (index_base) {
+            d.ix_state = reinterpret_cast<unsigned long long*>(index_base + index_offsets[i]);
+            d.ix_first = reinterpret_cast<uint32_t*>(d.ix_state + g.nsub);
+        }
+        if (g.nsub > max_nsub) max_nsub = g.nsub;
+        d.status = status + i;
+        const size_t px = (size_t)im.height * im.width;
+        if (px > max_pixels) max_pixels = px;
+    }
+    if (hipMemcpyAsync(dev, host, (size_t)n * sizeof(Img), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipEventRecord(P->staged[r], st) != hipSuccess)
+        return md2_report_error(MD2_ERR_HIP, "jpeg: staging the image table failed");
+    const uint8_t* huff = static_cast<const uint8_t*>(bank->huff);
+    const uint16_t* quant = static_cast<const uint16_t*>(bank->quant);
+    if (mode == kIndex) {   // the synchronisation alone: no coefficient, sample or pixel is written
+        hipLaunchKernelGGL(jpeg_entropy_kernel<true>, dim3(n), dim3(kThreads), 0, st, dev, huff, bank->num_huff);
+        const hipError_t e = hipGetLastError();
+        return e == hipSuccess ? MD2_OK : md2_report_error(MD2_ERR_HIP, hipGetErrorString(e));
+    }
+    if (hipMemsetAsync(P->workspace, 0, l.coef_bytes, st) != hipSuccess)
+        return md2_report_error(MD2_ERR_HIP, "jpeg: hipMemsetAsync failed");
+    if (mode == kRunIndexed) {
+        // several workgroups of an image OR into its status word: cleared here, not by one of them
+        if (hipMemsetAsync(status, 0, (size_t)n * sizeof(uint32_t), st) != hipSuccess)
+            return md2_report_error(MD2_ERR_HIP, "jpeg: hipMemsetAsync failed");
+        hipLaunchKernelGGL(jpeg_entropy_indexed_kernel, dim3((max_nsub + kIxThreads - 1) / kIxThreads, n),
+                           dim3(kIxThreads), 0, st, dev, huff, bank->num_huff);
+    } else {
+        hipLaunchKernelGGL(jpeg_entropy_kernel<false>, dim3(n), dim3(kThreads), 0, st, dev, huff, bank->num_huff);
+    }
+    hipLaunchKernelGGL(jpeg_dc_kernel, dim3(3, n), dim3(kThreads), 0, st, dev);
+    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((max_blocks + 255) / 256), 3 * n), dim3(256), 0, st, dev,
+                       quant, bank->num_quant);
+    size_t cb = (max_pixels + 255) / 256;
+    if (cb > 4096) cb = 4096;
+    hipLaunchKernelGGL(jpeg_colour_kernel, dim3((unsigned)cb, n), dim3(256), 0, st, dev);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? MD2_OK : md2_report_error(MD2_ERR_HIP, hipGetErrorString(e));
+}
+
 extern "C" {
 
 size_t md2_jpeg_workspace_bytes(const md2_jpeg_image* images, int n) {
@@ -639,7 +832,7 @@ size_t md2_jpeg_workspace_bytes(const md2_jpeg_image* images, int n) {
 int md2_jpeg_check(const md2_jpeg_image* images, int n, int num_quant, int num_huff, uint64_t streams_bytes,
                    uint64_t out_bytes) {
     if (const char* msg = check_batch(images, n)) return md2_report_error(MD2_ERR_ARG, msg);
-    if (const char* msg = check_ranges(images, n, num_quant, num_huff, streams_bytes, out_bytes))
+    if (const char* msg = check_ranges(images, n, num_quant, num_huff, streams_bytes, out_bytes, true))
         return md2_report_error(MD2_ERR_ARG, msg);
     return MD2_OK;
 }
@@ -683,75 +876,61 @@ int md2_jpeg_run(md2_jpeg_plan* P, const uint8_t* streams, uint64_t streams_byte
         return md2_report_error(MD2_ERR_ARG, "jpeg: plan/streams/images/bank/out/status is NULL");
     if (!bank->quant || !bank->huff) return md2_report_error(MD2_ERR_ARG, "jpeg: bank.quant/bank.huff is NULL");
     if (const char* msg = check_batch(images, n)) return md2_report_error(MD2_ERR_ARG, msg);
-    if (const char* msg = check_ranges(images, n, bank->num_quant, bank->num_huff, streams_bytes, out_bytes))
+    if (const char* msg = check_ranges(images, n, bank->num_quant, bank->num_huff, streams_bytes, out_bytes, true))
         return md2_report_error(MD2_ERR_ARG, msg);
-    if (reinterpret_cast<uintptr_t>(streams) % 4)
-        return md2_report_error(MD2_ERR_ARG, "jpeg: streams must be 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(bank->quant) % 16)
-        return md2_report_error(MD2_ERR_ARG, "jpeg: bank.quant must be 16-byte aligned");
-    if (n > P->max_images) return md2_report_error(MD2_ERR_ARG, "jpeg: more images than the plan was created for");
-    const Layout l = layout(images, n);
-    if (l.total > P->workspace_bytes)
-        return md2_report_error(MD2_ERR_ARG, "jpeg: the batch needs more workspace than the plan owns");
+    return run_chain(kRun, P, streams, images, nullptr, n, bank, out, nullptr, status, stream);
+}
 
-    hipStream_t st = (hipStream_t)stream;
-    const int r = P->slot;
-    P->slot = (P->slot + 1) % kRing;
-    if (hipEventSynchronize(P->staged[r]) != hipSuccess)
-        return md2_report_error(MD2_ERR_HIP, "jpeg: waiting for a staging slot failed");
-    Img* host = P->host_imgs + (size_t)r * P->max_images;
-    Img* dev = P->dev_imgs + (size_t)r * P->max_images;
-    size_t o_coef = 0, o_rest = l.coef_bytes, max_blocks = 0, max_pixels = 0;
-    for (int i = 0; i < n; ++i) {
-        const md2_jpeg_image& im = images[i];
-        const Geometry g = geometry(im);
-        Img& d = host[i];
-        memset(&d, 0, sizeof(d));
-        d.words = reinterpret_cast<const uint32_t*>(streams + im.stream_offset);
-        d.nbytes = im.stream_bytes;
-        d.h = im.height; d.w = im.width; d.hs = g.hs; d.vs = g.vs;
-        d.mcux = g.mcux; d.mcuy = g.mcuy; d.bpm = g.bpm;
-        d.total_blocks = (uint32_t)g.total_blocks;
-        size_t oc = o_coef, op = o_rest;
-        for (int c = 0; c < 3; ++c) {
-            d.qt[c] = im.quant[c]; d.dct[c] = im.dc[c]; d.act[c] = im.ac[c];
-            d.wb[c] = g.wb[c]; d.hb[c] = g.hb[c];
-            d.coef[c] = reinterpret_cast<int16_t*>(P->workspace + oc);
-            d.plane[c] = reinterpret_cast<uint8_t*>(P->workspace + op);
-            oc += g.blocks[c] * 64 * sizeof(int16_t);
-            op += g.blocks[c] * 64;
-            if (g.blocks[c] > max_blocks) max_blocks = g.blocks[c];
-        }
-        o_coef += align256(g.total_blocks * 64 * sizeof(int16_t));
-        o_rest += align256(g.total_blocks * 64);
-        d.slots = reinterpret_cast<unsigned long long*>(P->workspace + o_rest);
-        o_rest += align256(((size_t)g.nsub + 1) * sizeof(unsigned long long));
-        d.dirty = reinterpret_cast<uint32_t*>(P->workspace + o_rest);
-        o_rest += align256(((size_t)g.nsub + 1) * sizeof(uint32_t));
-        d.counts = reinterpret_cast<uint32_t*>(P->workspace + o_rest);
-        o_rest += align256((size_t)g.nsub * sizeof(uint32_t));
-        d.nsub = g.nsub;
-        d.out = out + im.out_offset;
-        d.status = status + i;
-        const size_t px = (size_t)im.height * im.width;
-        if (px > max_pixels) max_pixels = px;
-    }
-    if (hipMemcpyAsync(dev, host, (size_t)n * sizeof(Img), hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipEventRecord(P->staged[r], st) != hipSuccess)
-        return md2_report_error(MD2_ERR_HIP, "jpeg: staging the image table failed");
-    if (hipMemsetAsync(P->workspace, 0, l.coef_bytes, st) != hipSuccess)
-        return md2_report_error(MD2_ERR_HIP, "jpeg: hipMemsetAsync failed");
-    const uint8_t* huff = static_cast<const uint8_t*>(bank->huff);
-    const uint16_t* quant = static_cast<const uint16_t*>(bank->quant);
-    hipLaunchKernelGGL(jpeg_entropy_kernel, dim3(n), dim3(kThreads), 0, st, dev, huff, bank->num_huff);
-    hipLaunchKernelGGL(jpeg_dc_kernel, dim3(3, n), dim3(kThreads), 0, st, dev);
-    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((max_blocks + 255) / 256), 3 * n), dim3(256), 0, st, dev,
-                       quant, bank->num_quant);
-    size_t cb = (max_pixels + 255) / 256;
-    if (cb > 4096) cb = 4096;
-    hipLaunchKernelGGL(jpeg_colour_kernel, dim3((unsigned)cb, n), dim3(256), 0, st, dev);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MD2_OK : md2_report_error(MD2_ERR_HIP, hipGetErrorString(e));
+size_t md2_jpeg_index_bytes(uint32_t stream_bytes) {
+    md2_jpeg_image im = {};
+    im.stream_bytes = stream_bytes;
+    return index_size(stream_nsub(im));
+}
+
+int md2_jpeg_index(md2_jpeg_plan* P, const uint8_t* streams, uint64_t streams_bytes, const md2_jpeg_image* images,
+                   const uint64_t* index_offsets, int n, const md2_jpeg_bank* bank, uint8_t* index,
+                   uint64_t index_bytes, uint32_t* status, void* stream) {
+    if (!P || !streams || !images || !index_offsets || !bank || !index || !status)
+        return md2_report_error(MD2_ERR_ARG, "jpeg: plan/streams/images/index_offsets/bank/index/status is NULL");
+    if (!bank->quant || !bank->huff) return md2_report_error(MD2_ERR_ARG, "jpeg: bank.quant/bank.huff is NULL");
+    if (const char* msg = check_batch(images, n)) return md2_report_error(MD2_ERR_ARG, msg);
+    if (const char* msg = check_ranges(images, n, bank->num_quant, bank->num_huff, streams_bytes, 0, false))
+        return md2_report_error(MD2_ERR_ARG, msg);
+    if (const char* msg = check_index(images, index_offsets, n, index_bytes, "jpeg: an index reaches past index_bytes"))
+        return md2_report_error(MD2_ERR_ARG, msg);
+    if (reinterpret_cast<uintptr_t>(index) % 16)
+        return md2_report_error(MD2_ERR_ARG, "jpeg: index must be 16-byte aligned");
+    return run_chain(kIndex, P, streams, images, index_offsets, n, bank, nullptr, index, status, stream);
+}
+
+int md2_jpeg_check_indexed(const md2_jpeg_image* images, const uint64_t* index_offsets, int n, int num_quant,
+                           int num_huff, uint64_t streams_bytes, uint64_t out_bytes) {
+    if (!images || !index_offsets) return md2_report_error(MD2_ERR_ARG, "jpeg: images/index_offsets is NULL");
+    if (const char* msg = check_batch(images, n)) return md2_report_error(MD2_ERR_ARG, msg);
+    if (const char* msg = check_ranges(images, n, num_quant, num_huff, streams_bytes, out_bytes, true))
+        return md2_report_error(MD2_ERR_ARG, msg);
+    if (const char* msg =
+            check_index(images, index_offsets, n, streams_bytes, "jpeg: an index reaches past streams_bytes"))
+        return md2_report_error(MD2_ERR_ARG, msg);
+    return MD2_OK;
+}
+
+int md2_jpeg_run_indexed(md2_jpeg_plan* P, const uint8_t* streams, uint64_t streams_bytes,
+                         const md2_jpeg_image* images, const uint64_t* index_offsets, int n,
+                         const md2_jpeg_bank* bank, uint8_t* out, uint64_t out_bytes, uint32_t* status, void* stream) {
+    if (!P || !streams || !images || !index_offsets || !bank || !out || !status)
+        return md2_report_error(MD2_ERR_ARG, "jpeg: plan/streams/images/index_offsets/bank/out/status is NULL");
+    if (!bank->quant || !bank->huff) return md2_report_error(MD2_ERR_ARG, "jpeg: bank.quant/bank.huff is NULL");
+    if (const char* msg = check_batch(images, n)) return md2_report_error(MD2_ERR_ARG, msg);
+    if (const char* msg = check_ranges(images, n, bank->num_quant, bank->num_huff, streams_bytes, out_bytes, true))
+        return md2_report_error(MD2_ERR_ARG, msg);
+    if (const char* msg =
+            check_index(images, index_offsets, n, streams_bytes, "jpeg: an index reaches past streams_bytes"))
+        return md2_report_error(MD2_ERR_ARG, msg);
+    if (reinterpret_cast<uintptr_t>(streams) % 16)
+        return md2_report_error(MD2_ERR_ARG, "jpeg: streams must be 16-byte aligned when they carry indexes");
+    return run_chain(kRunIndexed, P, streams, images, index_offsets, n, bank, out, const_cast<uint8_t*>(streams),
+                     status, stream);
 }
 
 }  // extern "C"

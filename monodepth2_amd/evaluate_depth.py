@@ -131,10 +131,11 @@ def predict_from_disk(encoder, depth_decoder, opt, lines, feed_hw, device, batch
     the per-batch body of `predict_disparities`."""
     from .datasets import KITTIRAWDataset
     from .loader import BatchLoader
+    from .pack import open_pack
     dataset = KITTIRAWDataset(opt.data_path, lines, feed_hw[0], feed_hw[1], [0], 1, is_train=False,
                               img_ext=".png" if opt.png else ".jpg")
     loader = BatchLoader(dataset, batch_size, shuffle=False, drop_last=False, num_workers=opt.num_workers,
-                         device=device, device_decode=getattr(opt, "device_decode", False))
+                         device=device, device_decode=getattr(opt, "device_decode", False), pack=open_pack(opt))
     try:
         return _predict_batches(encoder, depth_decoder, (batch[("color", 0, 0)] for batch in loader),
                                 opt.post_process)

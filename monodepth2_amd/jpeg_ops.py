@@ -375,3 +375,186 @@ def decode_jpeg_batch(streams: Sequence[JpegStream], out: torch.Tensor, offsets:
                 raise RuntimeError(f"decode_jpeg_batch: stream index {bad[0]} did not decode "
                                    f"(status {int(status[bad[0]])}); bad indices {bad}")
     return status
+
+
+# ------------------------------------------------------------------ stored synchronisation indexes
+# md2_jpeg_index / md2_jpeg_run_indexed (include/md2hot.h): an image's index is nsub uint64 entry
+# states, then nsub uint32 first_block counts, zero padded to 16 bytes; here one uint8 array.
+SUB_BITS = 1024
+INDEX_ALIGN = 16
+
+
+def index_nsub(stream_bytes: int) -> int:
+    """Subsequences of a stream of `stream_bytes` bytes."""
+    return max(-(-8 * int(stream_bytes) // SUB_BITS), 1)
+
+
+def index_nbytes(stream_bytes: int) -> int:
+    """Bytes of the index of a stream of `stream_bytes` bytes (md2_jpeg_index_bytes)."""
+    return _align(12 * index_nsub(stream_bytes), INDEX_ALIGN)
+
+
+def pack_index(states: Sequence[int], first_blocks: Sequence[int]) -> np.ndarray:
+    """The index bytes of per-subsequence packed entry states (bit << 16 | block_in_mcu << 8 |
+    zigzag) and first_block counts."""
+    n = len(states)
+    if n < 1 or n != len(first_blocks):
+        raise ValueError(f"{n} states but {len(first_blocks)} first_block counts")
+    out = np.zeros(_align(12 * n, INDEX_ALIGN), np.uint8)
+    out[:8 * n] = np.asarray(states, dtype="<u8").view(np.uint8)
+    out[8 * n:12 * n] = np.asarray(first_blocks, dtype="<u4").view(np.uint8)
+    return out
+
+
+def unpack_index(index: np.ndarray, stream_bytes: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(states uint64[nsub], first_blocks uint32[nsub]) of the index of a stream of `stream_bytes` bytes."""
+    n = index_nsub(stream_bytes)
+    raw = np.ascontiguousarray(index, dtype=np.uint8).reshape(-1)
+    if raw.size != index_nbytes(stream_bytes):
+        raise ValueError(f"an index of {raw.size} bytes for a stream of {stream_bytes} bytes (expected "
+                         f"{index_nbytes(stream_bytes)})")
+    return raw[:8 * n].view("<u8").copy(), raw[8 * n:12 * n].view("<u4").copy()
+
+
+def _offset_array(values: Sequence[int]):
+    return (ctypes.c_uint64 * max(len(values), 1))(*[int(v) for v in values])
+
+
+def describe_batch_indexed(streams: Sequence[JpegStream], offsets: Sequence[int]):
+    """describe_batch for md2_jpeg_run_indexed: every stream has its index directly behind it
+    (16-byte aligned), so one contiguous range of the block is one frame.  Returns (images,
+    index_offsets, quant_tables, huff_tables, stream_base, total_bytes)."""
+    images, quant, huff, base, _ = describe_batch(streams, offsets)
+    pos, ix = 0, []
+    for i, s in enumerate(streams):
+        images[i].stream_offset = pos
+        pos += _align(len(s.data), INDEX_ALIGN)
+        ix.append(pos)
+        pos += index_nbytes(len(s.data))
+    return images, _offset_array(ix), quant, huff, base, base + max(pos, 16)
+
+
+def fill_staging_indexed(host: np.ndarray, streams, indexes, images, index_offsets, quant, huff, base: int):
+    """The staging block of describe_batch_indexed's layout written into `host` (uint8)."""
+    fill_staging(host, streams, images, quant, huff, base)
+    for i, s in enumerate(streams):
+        raw = np.ascontiguousarray(indexes[i], dtype=np.uint8).reshape(-1)
+        if raw.size != index_nbytes(len(s.data)):
+            raise ValueError(f"stream {i}: an index of {raw.size} bytes for {len(s.data)} stream bytes "
+                             f"(expected {index_nbytes(len(s.data))})")
+        o = base + index_offsets[i]
+        host[o:o + raw.size] = raw
+
+
+def check_described_indexed(images, index_offsets, n: int, num_quant: int, num_huff: int, streams_bytes: int,
+                            out_bytes: int):
+    """md2_jpeg_run_indexed's argument checks alone (host only): raises what it would refuse."""
+    _lib.check(_lib.lib().md2_jpeg_check_indexed(images, index_offsets, n, num_quant, num_huff, streams_bytes,
+                                                 out_bytes), "md2_jpeg_check_indexed")
+
+
+def run_staged_indexed(staged: torch.Tensor, images, index_offsets, n: int, num_quant: int, num_huff: int, base: int,
+                       total: int, out: torch.Tensor, device: torch.device) -> torch.Tensor:
+    """run_staged for a block of describe_batch_indexed's layout (or the loader's packed one:
+    tables, then records of stream + index): md2_jpeg_run_indexed's launches."""
+    L = _lib.lib()
+    need = L.md2_jpeg_workspace_bytes(images, n)
+    if need == 0:
+        _lib.check(-1, "md2_jpeg_workspace_bytes")
+    plan = _plan_for(device)
+    with torch.cuda.device(device):
+        plan.reserve(n, need)
+        ptr = staged.data_ptr()
+        bank = _lib.JpegBank(ptr, ptr + num_quant * _lib.JPEG_QUANT_BYTES, num_quant, num_huff)
+        _lib.check(L.md2_jpeg_run_indexed(plan.plan, ptr + base, total - base, images, index_offsets, n,
+                                          ctypes.byref(bank), out.data_ptr(), out.numel(), plan.status.data_ptr(),
+                                          _lib.stream(device)), "md2_jpeg_run_indexed")
+    return plan.status[:n]
+
+
+def _cuda_device(device, what: str) -> torch.device:
+    device = torch.device(device) if device is not None else torch.device("cuda")
+    if device.type != "cuda" or not torch.cuda.is_available():
+        raise RuntimeError(f"{what} is GPU only (HIP kernels, no CPU fallback)")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
+def index_jpeg_batch(streams: Sequence[JpegStream], device=None, check: bool = False) -> List[np.ndarray]:
+    """The synchronisation index of every stream (md2_jpeg_index: the entropy decoder's
+    fixed-point iteration alone, no frame decoded), as uint8 arrays of index_nbytes(len(
+    s.data)) bytes each: what decode_jpeg_batch_indexed and pack.write_pack take.  One upload,
+    one launch, one copy back; waits for the result.  check=True raises a RuntimeError for a
+    stream that does not hold exactly its image's blocks."""
+    device = _cuda_device(device, "index_jpeg_batch")
+    n = len(streams)
+    if n == 0:
+        return []
+    images, quant, huff, base, total = describe_batch(streams, [0] * n)
+    sizes = [index_nbytes(len(s.data)) for s in streams]
+    ix = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    index_offsets = _offset_array(ix[:-1].tolist())
+    L = _lib.lib()
+    need = L.md2_jpeg_workspace_bytes(images, n)
+    if need == 0:
+        _lib.check(-1, "md2_jpeg_workspace_bytes")
+    plan = _plan_for(device)
+    with torch.cuda.device(device):
+        pinned, staged, r = plan.stage(total)
+        fill_staging(pinned.numpy(), streams, images, quant, huff, base)
+        staged[:total].copy_(pinned[:total], non_blocking=True)
+        if plan.events[r] is None:
+            plan.events[r] = torch.cuda.Event()
+        plan.events[r].record()
+        plan.reserve(n, need)
+        dev_index = torch.empty(int(ix[-1]), dtype=torch.uint8, device=device)
+        ptr = staged.data_ptr()
+        bank = _lib.JpegBank(ptr, ptr + len(quant) * _lib.JPEG_QUANT_BYTES, len(quant), len(huff))
+        _lib.check(L.md2_jpeg_index(plan.plan, ptr + base, total - base, images, index_offsets, n, ctypes.byref(bank),
+                                    dev_index.data_ptr(), dev_index.numel(), plan.status.data_ptr(),
+                                    _lib.stream(device)), "md2_jpeg_index")
+        host = dev_index.cpu().numpy()          # waits for the launch
+        if check:
+            bad = torch.nonzero(plan.status[:n].cpu()).flatten().tolist()
+            if bad:
+                raise RuntimeError(f"index_jpeg_batch: stream index {bad[0]} does not hold its image's blocks "
+                                   f"(status {int(plan.status[bad[0]])}); bad indices {bad}")
+    return [host[ix[i]:ix[i + 1]].copy() for i in range(n)]
+
+
+def decode_jpeg_batch_indexed(streams: Sequence[JpegStream], indexes: Sequence[np.ndarray], out: torch.Tensor,
+                              offsets: Sequence[int], device=None, check: bool = False) -> torch.Tensor:
+    """decode_jpeg_batch from stored indexes (index_jpeg_batch's, or a pack's): the same
+    upload with every stream's index behind it, md2_jpeg_run_indexed's launches, the same
+    bytes in `out` and the same status words; a stream whose index does not fit it reports
+    JPEG_ST_INDEX, and the other frames of the batch are unaffected."""
+    device = torch.device(device) if device is not None else (out.device if torch.is_tensor(out) else None)
+    if device is None or device.type != "cuda" or not torch.is_tensor(out) or not out.is_cuda:
+        raise RuntimeError("decode_jpeg_batch_indexed is GPU only (HIP kernels, no CPU fallback)")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    if out.device != device or out.dtype != torch.uint8 or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous uint8 tensor on {device}")
+    n = len(streams)
+    if n != len(indexes):
+        raise ValueError(f"{n} streams but {len(indexes)} indexes")
+    if n == 0:
+        return torch.zeros(0, dtype=torch.int32, device=device)
+    images, index_offsets, quant, huff, base, total = describe_batch_indexed(streams, offsets)
+    check_described_indexed(images, index_offsets, n, len(quant), len(huff), total - base, out.numel())
+    plan = _plan_for(device)
+    with torch.cuda.device(device):
+        pinned, staged, r = plan.stage(total)
+        fill_staging_indexed(pinned.numpy(), streams, indexes, images, index_offsets, quant, huff, base)
+        staged[:total].copy_(pinned[:total], non_blocking=True)
+        if plan.events[r] is None:
+            plan.events[r] = torch.cuda.Event()
+        plan.events[r].record()
+        status = run_staged_indexed(staged, images, index_offsets, n, len(quant), len(huff), base, total, out, device)
+        if check:
+            bad = torch.nonzero(status.cpu()).flatten().tolist()
+            if bad:
+                raise RuntimeError(f"decode_jpeg_batch_indexed: stream index {bad[0]} did not decode "
+                                   f"(status {int(status[bad[0]])}); bad indices {bad}")
+    return status

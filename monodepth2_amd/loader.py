@@ -38,10 +38,19 @@ copy.  Every rule above stands.  The decoder's status words come back through pi
 behind the slot's event and are read when the slot is retired: a stream that did not decode
 raises a RuntimeError naming the split line and the file, one or two batches after its own
 or when the epoch ends.
+
+`pack=FramePack(...)` (pack.py) feeds the same device decoder from a packed
+frame file instead of the image files: sizes come from the pack's records and no file is
+opened; the producer thread lays the staging block out (the batch's table bank gathered from
+the records' ids, then every frame's record) and the decoding threads `os.preadv` each
+record, the stream with its synchronisation index behind it, straight into the slot's pinned
+buffer; the caller's thread launches `md2_jpeg_run_indexed`.  RAW records (files the device
+decoder does not take, stored decoded) ride the PIL frames' route.  Implies device_decode.
 """
 from __future__ import annotations
 
 import collections
+import ctypes
 import queue
 import random
 import threading
@@ -51,9 +60,10 @@ from typing import Dict, Iterator, List, Optional
 import numpy as np
 import torch
 
-from . import jpeg_ops
+from . import _lib, jpeg_ops
 from .augment import GpuAugmentMixed
 from .datasets import item_seed
+from .pack import KIND_JPEG, frame_key
 
 ALIGN = 256        # frame offsets in the ragged buffer
 MAX_THREADS = 16   # decoding threads, whatever --num_workers asks for
@@ -82,12 +92,13 @@ class _StagedJpeg:
         self.images, self.n, self.num_quant, self.num_huff = images, n, num_quant, num_huff
         self.base, self.jtotal = base, jtotal
         self.pil, self.frames_total, self.names = pil, frames_total, names
+        self.index_offsets = None   # a packed batch: where each stream's index lies, for md2_jpeg_run_indexed
 
 
 class BatchLoader:
     def __init__(self, dataset, batch_size: int, shuffle: bool = True, seed: int = 0, num_workers: int = 0,
                  rank: int = 0, world_size: int = 1, device=None, with_depth: bool = False, prefetch: int = 2,
-                 drop_last: bool = True, device_decode: bool = False):
+                 drop_last: bool = True, device_decode: bool = False, pack=None):
         if not (0 <= rank < world_size):
             raise ValueError(f"rank {rank} outside world size {world_size}")
         if not drop_last and world_size > 1:
@@ -107,7 +118,12 @@ class BatchLoader:
             raise ValueError("with_depth needs a dataset built with load_depth=True whose first split line has "
                              "ground truth (check_depth)")
         self.with_depth = with_depth
-        self.device_decode = bool(device_decode)
+        self.device_decode = bool(device_decode) or pack is not None
+        self.pack = pack
+        if pack is not None:   # every frame of every split line, before anything is built
+            lacking = pack.missing(dataset)
+            if lacking:
+                raise ValueError(lacking)
         self.prefetch = max(int(prefetch), 1)
         self.epoch = 0
         self.uploaded_bytes = 0   # host-to-device bytes of the batches handed out so far (tools/loader_bench.py)
@@ -178,9 +194,24 @@ class BatchLoader:
             raise errors[0]
         return items
 
+    def _open_packed(self, indices: List[int], epoch: int):
+        """Step 2 from a pack: the items with their sizes from the records; no file is opened.
+        Every item carries its frames' record rows in `rows`."""
+        items = []
+        for i in indices:
+            it = self.dataset.parse(i, epoch)
+            it.rows = [self.pack.row(frame_key(p, self.dataset.data_path)) for p in it.paths]
+            sizes = {self.pack._sizes[r] for r in it.rows}
+            if len(sizes) != 1:
+                raise ValueError(f"split line {i} ({it.line!r}): its frames decode to different sizes "
+                                 f"{sorted(sizes)}: {it.paths}")
+            it.size = sizes.pop()
+            items.append(it)
+        return items
+
     def _stage(self, indices: List[int], epoch: int, slot: int) -> _Staged:
         """Steps 2-3 for one batch into the free ring slot `slot`: host work only."""
-        items = self._open(indices, epoch)
+        items = self._open_packed(indices, epoch) if self.pack is not None else self._open(indices, epoch)
         try:
             F, B = len(self.frame_ids), len(items)
             offsets, total = [0] * (F * B), 0
@@ -188,6 +219,8 @@ class BatchLoader:
                 for b, it in enumerate(items):
                     offsets[f * B + b] = total
                     total += _padded(it.size)
+            if self.pack is not None:
+                return self._stage_packed(items, offsets, total, slot)
             if self.device_decode:
                 return self._stage_compressed(items, offsets, total, slot)
             buf, spill = self._pinned[slot], None
@@ -247,6 +280,66 @@ class BatchLoader:
         st.jpeg = _StagedJpeg(images, len(streams), len(quant), len(huff), base, jtotal, pil, frames_total, names)
         return st
 
+    def _stage_packed(self, items, offsets, frames_total: int, slot: int) -> _Staged:
+        """Step 3 from a pack: this (producer) thread lays out the block and gathers the table
+        bank from the records' ids; the decoding threads read every record into its place.
+        Host work only, and no byte of a stream is touched by the interpreter."""
+        F, B = len(self.frame_ids), len(items)
+        pack = self.pack
+        recs = pack.records
+        rows = [items[n % B].rows[n // B] for n in range(F * B)]
+        on_device = [n for n in range(F * B) if recs["kind"][rows[n]] == KIND_JPEG]
+        nj = len(on_device)
+        images = (_lib.JpegImage * max(nj, 1))()
+        index_offsets = (ctypes.c_uint64 * max(nj, 1))()
+        quant: Dict[int, int] = {}
+        huff: Dict[int, int] = {}
+        pos, reads = 0, []          # reads: (row, offset behind the tables or in the block, bytes)
+        for i, n in enumerate(on_device):
+            r = recs[rows[n]]
+            im = images[i]
+            im.height, im.width, im.sampling = int(r["height"]), int(r["width"]), int(r["sampling"])
+            im.out_offset, im.stream_bytes, im.stream_offset = offsets[n], int(r["stream_bytes"]), pos
+            for c in range(3):
+                im.quant[c] = quant.setdefault(int(r["quant"][c]), len(quant))
+                im.dc[c] = huff.setdefault(int(r["dc"][c]), len(huff))
+                im.ac[c] = huff.setdefault(int(r["ac"][c]), len(huff))
+            index_offsets[i] = pos + (im.stream_bytes + 15) // 16 * 16
+            reads.append((rows[n], pos, int(r["data_bytes"])))
+            pos += (int(r["data_bytes"]) + 15) // 16 * 16
+        if len(quant) > 255 or len(huff) > 255:
+            raise ValueError("more than 255 distinct tables in one batch: use a smaller batch")
+        nq, nh = len(quant) * _lib.JPEG_QUANT_BYTES, len(huff) * _lib.JPEG_HUFF_BYTES
+        base = (nq + nh + 15) // 16 * 16
+        jtotal = (base + max(pos, 16)) if nj else 0
+        if nj:
+            jpeg_ops.check_described_indexed(images, index_offsets, nj, len(quant), len(huff), jtotal - base,
+                                             frames_total)
+        reads = [(row, base + o, b) for row, o, b in reads]
+        pos, pil = jtotal, []
+        for n in range(F * B):
+            if recs["kind"][rows[n]] != KIND_JPEG:
+                pos = (pos + ALIGN - 1) // ALIGN * ALIGN
+                size = int(recs["data_bytes"][rows[n]])
+                pil.append((n, pos, size))
+                reads.append((rows[n], pos, size))
+                pos += size
+        total = max(pos, 16)
+        buf, spill = self._pinned[slot], None
+        if buf is None or buf.numel() < total:
+            host = spill = np.empty(total, dtype=np.uint8)
+        else:
+            host = buf.numpy()
+        if nj:
+            host[:nq] = pack.quant[list(quant)].reshape(-1)
+            host[nq:nq + nh] = pack.huff[list(huff)].reshape(-1)
+        self._map(lambda rd: pack.read_into(rd[0], host[rd[1]:rd[1] + rd[2]]), reads)
+        names = [(items[n % B].index, items[n % B].line, items[n % B].paths[n // B]) for n in on_device]
+        st = _Staged(slot, total, offsets, items, spill)
+        st.jpeg = _StagedJpeg(images, nj, len(quant), len(huff), base, jtotal, pil, frames_total, names)
+        st.jpeg.index_offsets = index_offsets
+        return st
+
     def _reserve(self, slot: int, total: int):
         """Slot `slot`'s pinned buffer holds `total` bytes (caller's thread; the slot is free)."""
         buf = self._pinned[slot]
@@ -282,8 +375,12 @@ class BatchLoader:
         j = st.jpeg
         frames = torch.empty(j.frames_total, dtype=torch.uint8, device=self.device)
         if j.n:
-            status = jpeg_ops.run_staged(up, j.images, j.n, j.num_quant, j.num_huff, j.base, j.jtotal, frames,
-                                         self.device)
+            if j.index_offsets is not None:
+                status = jpeg_ops.run_staged_indexed(up, j.images, j.index_offsets, j.n, j.num_quant, j.num_huff,
+                                                     j.base, j.jtotal, frames, self.device)
+            else:
+                status = jpeg_ops.run_staged(up, j.images, j.n, j.num_quant, j.num_huff, j.base, j.jtotal, frames,
+                                             self.device)
             host = self._status[st.slot]
             if host is None or host.numel() < j.n:
                 host = self._status[st.slot] = torch.empty(max(j.n, len(self.frame_ids) * self.batch_size),
@@ -303,9 +400,11 @@ class BatchLoader:
         bad = [(w, name) for w, name in zip(words, names) if w]
         if bad:
             w, (index, line, path) = bad[0]
+            why = ("the pack's synchronisation index does not fit the stream, or the stream does not hold the image's "
+                   "blocks" if w & _lib.JPEG_ST_INDEX
+                   else "the entropy-coded data does not hold the image's blocks")
             raise RuntimeError(f"split line {index} ({line!r}): {path} did not decode on the device (status {w}: "
-                               f"the entropy-coded data does not hold the image's blocks); {len(bad)} bad "
-                               "file(s) in its batch")
+                               f"{why}); {len(bad)} bad file(s) in its batch")
 
     # -------------------------------------------------------------- iteration
     def __iter__(self) -> Iterator[Dict]:
@@ -316,7 +415,7 @@ class BatchLoader:
             return
         # every slot is free once the uploads of an earlier epoch have run; the ring is
         # sized here, before the producer starts, from the first batch's headers
-        first = self._open(todo[0], epoch)
+        first = self._open_packed(todo[0], epoch) if self.pack is not None else self._open(todo[0], epoch)
         for it in first:
             it.close()
         need = len(self.frame_ids) * sum(_padded(it.size) for it in first)

@@ -25,6 +25,9 @@ _FLAGS = [
     ("--png", dict(action="store_true", help="train from png instead of jpg")),
     ("--device_decode", dict(action="store_true", help="decode baseline JPEG frames on the GPU (HIP kernels, "
                                                         "bit-equal to PIL); other files still go through PIL")),
+    ("--pack", dict(type=str, help="build: feed the frames from this packed frame file (python -m "
+                                   "monodepth2_amd.pack_dataset) instead of the image files under --data_path; "
+                                   "implies --device_decode; ground-truth depth is still read from --data_path")),
     ("--height", dict(type=int, default=192, help="input height")),
     ("--width", dict(type=int, default=640, help="input width")),
     ("--disparity_smoothness", dict(type=float, default=1e-3, help="smoothness weight")),

@@ -1,0 +1,379 @@
+"""A packed frame file: every frame of a KITTI tree parsed, unstuffed and indexed once.
+
+`build_pack` names the frames of some split lists through the dataset classes
+(`parse(i).paths`), reads each file once, and writes one file that holds, per frame, what
+the device decoder needs with no further host work: the unstuffed entropy-coded stream
+(jpeg_ops.parse_jpeg), ids of its quantisation and Huffman tables, and the stream's
+synchronisation index (jpeg_ops.index_jpeg_batch: the entry state of every 1024-bit
+subsequence, found once on the device) directly behind it.  A file the device decoder does
+not take (PNG, progressive, ...) is stored as its PIL-decoded RGB bytes, kind RAW, so a
+batch from the pack is always bit-equal to the same batch from disk.  `FramePack` opens such
+a file; `loader.BatchLoader(pack=...)` then feeds the step with an index lookup and one
+`os.preadv` per frame, straight into pinned memory.
+
+The file (version 1; little-endian; every section 16-byte aligned; the header is written
+last, so a build that died leaves no magic):
+
+  header    128 bytes: magic "MD2PACK\\0", u32 version, u32 record_bytes (96), u64 file_bytes,
+            u64 num_records, u32 num_quant, u32 num_huff, u64 offsets of the quant, huff,
+            records and names sections, u64 names_bytes, u64 data_offset (128), zeros
+  data      per record one contiguous 16-byte aligned range.  JPEG: the stream
+            (stream_bytes), zeros to 16, then its index (nsub u64 states, nsub u32
+            first_blocks, zeros to 16; nsub = max(ceil(8 * stream_bytes / 1024), 1)).
+            RAW: height * width * 3 bytes of RGB.
+  quant     num_quant tables of 64 u16 in natural order   } the layout of md2_jpeg_bank:
+  huff      num_huff tables of 16 counts + 256 values     } a batch's bank is a gather by id
+  records   num_records x 96 bytes, sorted by name: u32 kind (0 JPEG, 1 RAW), height, width,
+            sampling; u64 data_offset, data_bytes; u32 stream_bytes, name_offset, name_bytes;
+            u32 quant[3], dc[3], ac[3] (table ids); zeros
+  names     the keys, UTF-8, back to back: a frame's path relative to --data_path with "/"
+
+Equal tables are stored once; files written with optimised coding carry their own, so the
+ids are 32-bit and the at most 255 tables of one batch are numbered per batch.
+"""
+from __future__ import annotations
+
+import os
+import struct
+from concurrent.futures import ThreadPoolExecutor
+from typing import Dict, Iterable, Iterator, List, Optional, Sequence, Tuple
+
+import numpy as np
+from PIL import Image
+
+from . import jpeg_ops
+from ._lib import JPEG_HUFF_BYTES, JPEG_QUANT_BYTES
+
+MAGIC = b"MD2PACK\0"
+VERSION = 1
+HEADER_BYTES = 128
+KIND_JPEG, KIND_RAW = 0, 1
+_HEADER = struct.Struct("<8sIIQQIIQQQQQQ")
+RECORD = np.dtype([("kind", "<u4"), ("height", "<u4"), ("width", "<u4"), ("sampling", "<u4"),
+                   ("data_offset", "<u8"), ("data_bytes", "<u8"),
+                   ("stream_bytes", "<u4"), ("name_offset", "<u4"), ("name_bytes", "<u4"),
+                   ("quant", "<u4", 3), ("dc", "<u4", 3), ("ac", "<u4", 3), ("reserved", "u1", 16)])
+assert RECORD.itemsize == 96 and _HEADER.size <= HEADER_BYTES
+
+
+class PackError(ValueError):
+    """A file that is no frame pack of this version, or a damaged one."""
+
+
+def _align16(n: int) -> int:
+    return (n + 15) // 16 * 16
+
+
+def frame_key(path: str, data_path: str) -> str:
+    """A frame's key in a pack: its path relative to the dataset root, with "/"."""
+    root = os.path.join(data_path, "")
+    rel = path[len(root):] if path.startswith(root) else os.path.relpath(path, data_path)
+    return rel.replace(os.sep, "/")
+
+
+class PackRecord:
+    """One frame on its way into a pack.  JPEG: `stream` (a jpeg_ops.JpegStream) and `index`
+    (its index bytes, jpeg_ops.index_jpeg_batch's or pack_index's).  RAW: `raw`, the decoded
+    (h, w, 3) uint8 RGB frame."""
+    __slots__ = ("name", "stream", "index", "raw")
+
+    def __init__(self, name: str, stream=None, index=None, raw=None):
+        if (stream is None) == (raw is None):
+            raise ValueError(f"{name}: a record is either a stream with its index or raw RGB")
+        if stream is not None:
+            index = np.ascontiguousarray(index, dtype=np.uint8).reshape(-1)
+            if index.size != jpeg_ops.index_nbytes(len(stream.data)):
+                raise ValueError(f"{name}: an index of {index.size} bytes for a stream of {len(stream.data)} bytes "
+                                 f"(expected {jpeg_ops.index_nbytes(len(stream.data))})")
+        else:
+            raw = np.ascontiguousarray(raw, dtype=np.uint8)
+            if raw.ndim != 3 or raw.shape[2] != 3:
+                raise ValueError(f"{name}: raw frames are (h, w, 3) uint8, not {raw.shape}")
+        self.name, self.stream, self.index, self.raw = name, stream, index, raw
+
+
+def _huff_bytes(counts, vals) -> bytes:
+    return bytes(counts) + bytes(vals) + b"\0" * (JPEG_HUFF_BYTES - 16 - len(vals))
+
+
+def write_pack(path: str, records: Iterable[PackRecord]) -> int:
+    """Writes the records (any order, any iterable: data is written as it arrives) to `path`;
+    returns their number.  Records already carry their index.  Two records of one name are
+    refused."""
+    quant: Dict[bytes, int] = {}
+    huff: Dict[bytes, int] = {}
+    rows: List[Tuple] = []
+    seen = set()
+    with open(path, "wb") as f:
+        f.write(b"\0" * HEADER_BYTES)
+        pos = HEADER_BYTES
+        for rec in records:
+            if rec.name in seen:
+                raise ValueError(f"{rec.name}: twice in one pack")
+            seen.add(rec.name)
+            if rec.stream is not None:
+                s = rec.stream
+                pad = _align16(len(s.data)) - len(s.data)
+                f.write(s.data)
+                f.write(b"\0" * pad)
+                f.write(rec.index.tobytes())
+                nbytes = len(s.data) + pad + rec.index.size
+                q = [quant.setdefault(np.asarray(s.quant[c], dtype="<u2").tobytes(), len(quant)) for c in range(3)]
+                dc = [huff.setdefault(_huff_bytes(*s.huff[(0, s.dc[c])]), len(huff)) for c in range(3)]
+                ac = [huff.setdefault(_huff_bytes(*s.huff[(1, s.ac[c])]), len(huff)) for c in range(3)]
+                rows.append((rec.name, KIND_JPEG, s.height, s.width, s.sampling, pos, nbytes, len(s.data), q, dc, ac))
+            else:
+                h, w = rec.raw.shape[:2]
+                f.write(rec.raw.tobytes())
+                nbytes = _align16(h * w * 3)
+                f.write(b"\0" * (nbytes - h * w * 3))
+                rows.append((rec.name, KIND_RAW, h, w, 0, pos, h * w * 3, 0, [0] * 3, [0] * 3, [0] * 3))
+            pos += nbytes
+        rows.sort(key=lambda r: r[0])
+        table = np.zeros(len(rows), RECORD)
+        names = bytearray()
+        for i, (name, kind, h, w, sampling, off, nbytes, sbytes, q, dc, ac) in enumerate(rows):
+            key = name.encode("utf-8")
+            table[i] = (kind, h, w, sampling, off, nbytes, sbytes, len(names), len(key), q, dc, ac,
+                        np.zeros(16, np.uint8))
+            names += key
+        quant_off = pos
+        f.write(b"".join(quant))                      # dicts keep insertion order: id order
+        huff_off = quant_off + _align16(len(quant) * JPEG_QUANT_BYTES)
+        f.seek(huff_off)
+        f.write(b"".join(huff))
+        rec_off = huff_off + _align16(len(huff) * JPEG_HUFF_BYTES)
+        f.seek(rec_off)
+        f.write(table.tobytes())
+        names_off = rec_off + _align16(table.nbytes)
+        f.seek(names_off)
+        f.write(bytes(names))
+        total = _align16(names_off + len(names))
+        f.truncate(total)
+        f.seek(0)
+        f.write(_HEADER.pack(MAGIC, VERSION, RECORD.itemsize, total, len(rows), len(quant), len(huff), quant_off,
+                             huff_off, rec_off, names_off, len(names), HEADER_BYTES))
+    return len(rows)
+
+
+class FramePack:
+    """A pack opened for reading: the header validated, the tables, records and names in
+    memory, the data left on disk behind one file descriptor (`read_into`, thread-safe)."""
+
+    def __init__(self, path: str):
+        self.path = str(path)
+        self._fd = None
+        size = os.path.getsize(self.path)
+        with open(self.path, "rb") as f:
+            head = f.read(HEADER_BYTES)
+            if len(head) < HEADER_BYTES:
+                raise PackError(f"{self.path}: truncated: {len(head)} bytes, a pack header has {HEADER_BYTES}")
+            (magic, version, rbytes, total, n, nq, nh, q_off, h_off, r_off, n_off, n_bytes,
+             d_off) = _HEADER.unpack_from(head)
+            if magic != MAGIC:
+                raise PackError(f"{self.path}: wrong magic {magic!r}: not a frame pack (or one whose build did not "
+                                "finish)")
+            if version != VERSION or rbytes != RECORD.itemsize:
+                raise PackError(f"{self.path}: wrong version {version} (records of {rbytes} bytes): this build reads "
+                                f"version {VERSION} (records of {RECORD.itemsize} bytes)")
+            if size < total:
+                raise PackError(f"{self.path}: truncated: {size} bytes on disk, the header says {total}")
+            ends = [(q_off, nq * JPEG_QUANT_BYTES), (h_off, nh * JPEG_HUFF_BYTES), (r_off, n * rbytes),
+                    (n_off, n_bytes)]
+            if d_off != HEADER_BYTES or any(o % 16 or o < d_off or o + b > total for o, b in ends):
+                raise PackError(f"{self.path}: a section lies outside the file's {total} bytes")
+
+            def section(off, nbytes):
+                f.seek(off)
+                b = f.read(nbytes)
+                if len(b) != nbytes:
+                    raise PackError(f"{self.path}: truncated inside a section")
+                return b
+
+            self.quant = np.frombuffer(section(q_off, nq * JPEG_QUANT_BYTES), np.uint8).reshape(nq, JPEG_QUANT_BYTES)
+            self.huff = np.frombuffer(section(h_off, nh * JPEG_HUFF_BYTES), np.uint8).reshape(nh, JPEG_HUFF_BYTES)
+            self.records = np.frombuffer(section(r_off, n * rbytes), RECORD)
+            names = section(n_off, n_bytes)
+        self.file_bytes = total
+        r = self.records
+        if n:
+            jpeg = r["kind"] == KIND_JPEG
+            if (np.any(r["data_offset"] % 16) or np.any(r["data_offset"] < d_off)
+                    or np.any(r["data_offset"] + r["data_bytes"] > q_off) or np.any(r["kind"] > KIND_RAW)
+                    or np.any(r["name_offset"].astype(np.uint64) + r["name_bytes"] > n_bytes)
+                    or np.any(r["quant"][jpeg] >= nq) or np.any(r["dc"][jpeg] >= nh) or np.any(r["ac"][jpeg] >= nh)):
+                raise PackError(f"{self.path}: a record points outside its section")
+        self.names = [names[int(o):int(o) + int(b)].decode("utf-8") for o, b in zip(r["name_offset"], r["name_bytes"])]
+        self._row = {name: i for i, name in enumerate(self.names)}
+        # what the loader asks per frame, as plain Python values
+        self._sizes = [(int(h), int(w)) for h, w in zip(r["height"], r["width"])]
+        self._fd = os.open(self.path, os.O_RDONLY)
+
+    def __len__(self):
+        return len(self.names)
+
+    def __contains__(self, key: str):
+        return key in self._row
+
+    def row(self, key: str) -> int:
+        try:
+            return self._row[key]
+        except KeyError:
+            raise KeyError(f"{key} is not in the pack {self.path}") from None
+
+    def record(self, key: str):
+        """The record (a numpy row of dtype RECORD) of the frame with key `key`."""
+        return self.records[self.row(key)]
+
+    def size(self, key: str) -> Tuple[int, int]:
+        """(height, width) of the frame with key `key`."""
+        return self._sizes[self.row(key)]
+
+    def read_into(self, row: int, dest: np.ndarray):
+        """Record `row`'s byte range read into `dest` (uint8, data_bytes long): one preadv."""
+        rec = self.records[row]
+        want = int(rec["data_bytes"])
+        got = os.preadv(self._fd, [memoryview(dest)], int(rec["data_offset"]))
+        while 0 < got < want:       # a short read continues where it stopped
+            more = os.preadv(self._fd, [memoryview(dest)[got:]], int(rec["data_offset"]) + got)
+            if more <= 0:
+                break
+            got += more
+        if got != want:
+            raise IOError(f"{self.path}: {got} of {want} bytes read for {self.names[row]}")
+
+    def read(self, key: str) -> np.ndarray:
+        """The frame's bytes: stream, padding and index of a JPEG record, RGB of a RAW one."""
+        row = self.row(key)
+        out = np.empty(int(self.records[row]["data_bytes"]), np.uint8)
+        self.read_into(row, out)
+        return out
+
+    def stream(self, key: str):
+        """(JpegStream, index bytes) of a JPEG record, as write_pack took them."""
+        rec = self.record(key)
+        if rec["kind"] != KIND_JPEG:
+            raise ValueError(f"{key} is a RAW record")
+        data = self.read(key)
+        n = int(rec["stream_bytes"])
+        huff, dc, ac = {}, [], []
+        for c in range(3):
+            for cls, ids, out in ((0, rec["dc"], dc), (1, rec["ac"], ac)):
+                t = self.huff[int(ids[c])]
+                counts = tuple(int(x) for x in t[:16])
+                huff[(cls, int(ids[c]))] = (counts, t[16:16 + sum(counts)].tobytes())
+                out.append(int(ids[c]))
+        quant = tuple(tuple(int(x) for x in self.quant[int(rec["quant"][c])].view("<u2")) for c in range(3))
+        factors = {v: k for k, v in jpeg_ops.SAMPLINGS.items()}[int(rec["sampling"])]
+        s = jpeg_ops.JpegStream(int(rec["height"]), int(rec["width"]), int(rec["sampling"]), factors, quant, huff,
+                                tuple(dc), tuple(ac), data[:n].tobytes())
+        return s, data[_align16(n):].copy()
+
+    def missing(self, dataset) -> Optional[str]:
+        """None if the pack holds every frame of every split line of `dataset`, else a
+        sentence naming the first line and path it lacks."""
+        for i in range(len(dataset)):
+            item = dataset.parse(i)
+            for p in item.paths:
+                if frame_key(p, dataset.data_path) not in self._row:
+                    return (f"split line {i} ({item.line!r}): {p} is not in the pack {self.path} "
+                            f"(key {frame_key(p, dataset.data_path)!r}; {len(self)} frames packed)")
+        return None
+
+    def covers(self, dataset) -> bool:
+        """Whether the pack holds every frame of every split line of `dataset` (`missing` says which not)."""
+        return self.missing(dataset) is None
+
+    def close(self):
+        if self._fd is not None:
+            os.close(self._fd)
+            self._fd = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def open_pack(opt) -> Optional[FramePack]:
+    """The pack --pack names, or None without the flag."""
+    path = getattr(opt, "pack", None)
+    return FramePack(path) if path else None
+
+
+def frame_paths(data_path: str, line_lists: Sequence[Sequence[str]], dataset: str = "kitti", png: bool = False,
+                frame_ids: Sequence = (0, -1, 1), use_stereo: bool = False) -> Dict[str, str]:
+    """{key: path} of every frame the split lines name, through the dataset class's own
+    `parse(i).paths`, deduplicated."""
+    from .datasets import DATASETS
+    if dataset not in DATASETS:
+        raise ValueError(f"--dataset {dataset} cannot be packed: choose one of {sorted(DATASETS)}")
+    ids = list(frame_ids) + (["s"] if use_stereo and "s" not in frame_ids else [])
+    out: Dict[str, str] = {}
+    for lines in line_lists:
+        ds = DATASETS[dataset](data_path, list(lines), 192, 640, ids, 4, is_train=False,
+                               img_ext=".png" if png else ".jpg")
+        for i in range(len(ds)):
+            for p in ds.parse(i).paths:
+                out.setdefault(frame_key(p, data_path), p)
+    return out
+
+
+def records_from_files(paths: Dict[str, str], device=None, batch: int = 64,
+                       threads: int = 8) -> Iterator[PackRecord]:
+    """The records of the files {key: path}, in key order: read and parsed by `threads` host
+    threads, the supported JPEG files indexed on the device `batch` at a time, every other
+    file decoded with PIL into a RAW record."""
+    def load(key):
+        path = paths[key]
+        try:
+            with open(path, "rb") as f:
+                data = f.read()
+        except FileNotFoundError:
+            raise FileNotFoundError(f"no such image file {path} (frame {key})") from None
+        s = jpeg_ops.parse_jpeg(data)
+        if s is not None:
+            return s
+        with Image.open(path) as im:
+            return np.asarray(im.convert("RGB"))
+
+    keys = sorted(paths)
+    with ThreadPoolExecutor(max(threads, 1)) as pool:
+        for start in range(0, len(keys), batch):
+            chunk = keys[start:start + batch]
+            got = list(pool.map(load, chunk))
+            on_device = [n for n, g in enumerate(got) if isinstance(g, jpeg_ops.JpegStream)]
+            indexes = dict(zip(on_device, jpeg_ops.index_jpeg_batch([got[n] for n in on_device], device)))
+            for n, key in enumerate(chunk):
+                if n in indexes:
+                    yield PackRecord(key, stream=got[n], index=indexes[n])
+                else:
+                    yield PackRecord(key, raw=got[n])
+
+
+def build_pack(out: str, data_path: str, line_lists: Sequence[Sequence[str]], dataset: str = "kitti",
+               png: bool = False, frame_ids: Sequence = (0, -1, 1), use_stereo: bool = False, device=None,
+               batch: int = 64, threads: int = 8) -> Dict:
+    """Parse, index on the device, write: the frames the split lines of `line_lists` name
+    under `data_path`, into the pack `out`.  Files are read by `threads` host threads and
+    indexed `batch` at a time.  Returns {"frames", "jpeg", "raw", "pack_bytes", "file_bytes"}
+    (file_bytes: the size of the image files read)."""
+    paths = frame_paths(data_path, line_lists, dataset, png, frame_ids, use_stereo)
+    stats = {"frames": 0, "jpeg": 0, "raw": 0, "file_bytes": 0}
+
+    def counted():
+        for rec in records_from_files(paths, device, batch, threads):
+            stats["jpeg" if rec.stream is not None else "raw"] += 1
+            stats["file_bytes"] += os.path.getsize(paths[rec.name])
+            yield rec
+
+    tmp = out + ".tmp"
+    try:
+        stats["frames"] = write_pack(tmp, counted())
+        os.replace(tmp, out)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+    stats["pack_bytes"] = os.path.getsize(out)
+    return stats

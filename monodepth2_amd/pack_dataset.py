@@ -1,0 +1,40 @@
+"""Pack a KITTI tree once: `python -m monodepth2_amd.pack_dataset --data_path ROOT --lists
+train_files.txt val_files.txt ... --out FILE`.
+
+Reads the split lists, names their frames as `train` / `evaluate_depth` / `evaluate_pose`
+would (--dataset, --png, --frame_ids and --use_stereo as there), and writes the frame pack
+`--pack FILE` of those commands reads (pack.py).  Needs the GPU: the
+synchronisation indexes are computed by the device decoder's own kernel.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+from typing import Optional, Sequence
+
+from .datasets import DATASETS, readlines
+from .pack import build_pack
+
+
+def main(argv: Optional[Sequence[str]] = None):
+    ap = argparse.ArgumentParser(description="Write a frame pack for --pack (MI355X build)")
+    ap.add_argument("--data_path", required=True, help="dataset root, as for train")
+    ap.add_argument("--lists", nargs="+", required=True, help="split list files whose frames to pack")
+    ap.add_argument("--out", required=True, help="the pack to write")
+    ap.add_argument("--dataset", default="kitti", choices=sorted(DATASETS))
+    ap.add_argument("--png", action="store_true", help="the tree holds png files")
+    ap.add_argument("--frame_ids", nargs="+", type=int, default=[0, -1, 1])
+    ap.add_argument("--use_stereo", action="store_true", help="also pack the other camera of every line")
+    ap.add_argument("--batch", type=int, default=64, help="files indexed per device call")
+    ap.add_argument("--threads", type=int, default=8, help="host threads reading and parsing files (at most 16)")
+    args = ap.parse_args(argv)
+    stats = build_pack(args.out, args.data_path, [readlines(p) for p in args.lists], dataset=args.dataset,
+                       png=args.png, frame_ids=args.frame_ids, use_stereo=args.use_stereo, batch=args.batch,
+                       threads=min(max(args.threads, 1), 16))
+    stats["out"] = args.out
+    print(json.dumps(stats))
+    return stats
+
+
+if __name__ == "__main__":
+    main()

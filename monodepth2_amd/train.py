@@ -21,6 +21,7 @@ from .datasets import DATASETS, readlines
 from .distributed import init_process_group
 from .loader import BatchLoader
 from .options import MonodepthOptions
+from .pack import open_pack
 from .trainer import Trainer
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -49,7 +50,7 @@ def build_loaders(opt, trainer: Trainer):
     frame_ids = list(trainer.opt.frame_ids)   # with "s" appended under --use_stereo
     common = dict(batch_size=opt.batch_size, shuffle=True, num_workers=opt.num_workers, rank=trainer.rank,
                   world_size=trainer.world_size, device=trainer.device,
-                  device_decode=getattr(opt, "device_decode", False))
+                  device_decode=getattr(opt, "device_decode", False), pack=open_pack(opt))
     train_set = cls(opt.data_path, train_lines, opt.height, opt.width, frame_ids, num_scales, is_train=True,
                     img_ext=img_ext, seed=opt.seed)
     # depth_gt feeds the validation monitor only (Trainer.val_step)
