@@ -1091,6 +1091,68 @@ int md2_jpeg_run_indexed(md2_jpeg_plan* plan, const uint8_t* streams, uint64_t s
                          const md2_jpeg_bank* bank, uint8_t* out, uint64_t out_bytes, uint32_t* status, void* stream);
 
 /*
+ * Baseline JPEG encoding on the device (csrc/jpegenc.hip): the other half of md2_jpeg_run.
+ * Tight (h, w, 3) uint8 RGB frames of mixed sizes -> the entropy-coded segment of each,
+ * UNSTUFFED (no FF 00; what md2_jpeg_image.stream_bytes describes and a pack record holds),
+ * the last partial byte filled with 1-bits.  Every byte is what libjpeg's default integer
+ * path (the one Pillow uses) writes for the frame at the same tables and sampling: 16-bit
+ * fixed-point RGB -> YCbCr, box downsampling with the alternating bias (no smoothing), edges
+ * by repetition, jfdctint's islow forward transform, quantisation by 8 q rounding half away
+ * from zero, one interleaved scan without restart markers, the four standard Huffman tables
+ * of ITU-T T.81 Annex K (compiled in; there are no optimised tables).  The host writes the
+ * file around the segment (monodepth2_amd/jpeg_ops.py).  Integer arithmetic only; the only
+ * atomics are integer ORs on the words two neighbouring blocks share: two runs are
+ * bit-equal.  New symbols under ABI 24, no version bump (as md2_jpeg_index).
+ *
+ * in: device bytes; frame i is height * width * 3 bytes at in_offset.  images: HOST array of
+ * n, read for the checks and the launch sizes only; dev_images: a DEVICE copy of the same
+ * array (8-byte aligned), which the kernels read, so the caller uploads it with the frames
+ * and the call stages nothing.  quant: DEVICE bank of num_quant tables of 64 uint16 in
+ * natural (row-major) order, the layout of md2_jpeg_bank.quant; an image names its luma and
+ * its chroma table.  out: device bytes, 16-byte aligned; image i owns out_capacity bytes at
+ * out_offset (a multiple of 16).  Whole 32-bit words take the OR, so a range is rounded up
+ * to 4 bytes for the bounds check against out_bytes (rounded up likewise); the bytes of that
+ * last word beyond the capacity are OR-ed with zeros and keep their value.  workspace:
+ * device bytes, 256-byte aligned, md2_jpeg_encode_workspace_bytes of the batch, no
+ * initialisation needed.  stream_bytes, status: device uint32[n], written by the call:
+ * the stream's length (also when it does not fit, so the caller can size a second call) and
+ * 0 or MD2_JPEGENC_ST_SPACE.  A stream that does not fit its capacity writes nothing of its
+ * range; no byte outside an image's range is written in either case and the other images of
+ * the batch are unaffected.  Bit offsets are 64-bit, so no batch is too long.
+ *
+ * A fixed chain of launches on `stream` (setup, dct + quantise, bit count, per-image scan,
+ * zero, emit): no allocation, no host synchronisation, hipGraph-capturable.  Refused
+ * (MD2_ERR_ARG) before anything is launched: NULL arguments, n outside 1..4096, a height or
+ * width outside 1..8192, an unknown sampling class, num_quant outside 1..256, a table index
+ * outside the bank, a frame that leaves in_bytes, an out_offset that is no multiple of 16,
+ * an output range that leaves out_bytes, misaligned buffers, a workspace that is too small.
+ * md2_jpeg_encode_check runs the checks that need no pointer alone (host only, launches
+ * nothing).  md2_jpeg_encode_bound: a capacity no stream of that geometry exceeds (a block
+ * is at most 20 + 63 * 26 = 1658 bits: 208 bytes per block, dummy blocks included), 0 (and
+ * md2_last_error) for a geometry the encoder refuses.
+ */
+#define MD2_JPEGENC_ST_SPACE (1u << 0)   /* the stream does not fit out_capacity */
+
+typedef struct md2_jpegenc_image {
+    uint64_t in_offset;             /* bytes into in: the tight (height, width, 3) frame */
+    uint64_t out_offset;            /* bytes into out, a multiple of 16 */
+    uint32_t out_capacity;          /* bytes of the output range */
+    int32_t height, width;          /* 1..8192 */
+    int32_t sampling;               /* MD2_JPEG_444 / 422 / 420 */
+    uint8_t quant[2];               /* luma, chroma: indices into the quant bank */
+    uint8_t reserved[6];            /* 0; the struct is 40 bytes */
+} md2_jpegenc_image;
+
+size_t md2_jpeg_encode_bound(int height, int width, int sampling);
+size_t md2_jpeg_encode_workspace_bytes(const md2_jpegenc_image* images, int n);
+int md2_jpeg_encode_check(const md2_jpegenc_image* images, int n, int num_quant, uint64_t in_bytes,
+                          uint64_t out_bytes);
+int md2_jpeg_encode(const uint8_t* in, uint64_t in_bytes, const md2_jpegenc_image* images,
+                    const md2_jpegenc_image* dev_images, int n, const uint16_t* quant, int num_quant, uint8_t* out,
+                    uint64_t out_bytes, void* workspace, size_t workspace_bytes, uint32_t* stream_bytes,
+                    uint32_t* status, void* stream);
+
+/*
  * The training log's pictures (csrc/md2hot.hip): what the reference's Trainer.log writes at
  * a log step (trainer.py:540-572, with normalize_image, utils.py:22-28) for the first
  * `items` images of the batch, as one uint8 contact sheet (items, sheet_h, sheet_w, 3) filled

@@ -81,6 +81,7 @@ EXPORTS = ["md2_abi_version", "md2_last_error", "md2_workspace_bytes", "md2_sele
            "md2_jpeg_workspace_bytes", "md2_jpeg_check", "md2_jpeg_plan_create", "md2_jpeg_plan_destroy",
            "md2_jpeg_run",
            "md2_jpeg_index_bytes", "md2_jpeg_index", "md2_jpeg_check_indexed", "md2_jpeg_run_indexed",
+           "md2_jpeg_encode_bound", "md2_jpeg_encode_workspace_bytes", "md2_jpeg_encode_check", "md2_jpeg_encode",
            "md2_log_panel_tile_blocks", "md2_log_panel_check", "md2_log_panel_workspace_bytes", "md2_log_panel",
            "md2_depth_points", "md2_depth_points_workspace_bytes"]
 
@@ -252,6 +253,17 @@ class JpegBank(ctypes.Structure):
     _fields_ = [("quant", _vp), ("huff", _vp), ("num_quant", ctypes.c_int32), ("num_huff", ctypes.c_int32)]
 
 
+# md2_jpeg_encode (csrc/jpegenc.hip): new symbols under ABI 24, no version bump
+JPEGENC_ST_SPACE = 1     # the stream does not fit its output range
+JPEGENC_BLOCK_BYTES = 208   # md2_jpeg_encode_bound per block of the scan
+
+
+class JpegEncImage(ctypes.Structure):
+    _fields_ = [("in_offset", ctypes.c_uint64), ("out_offset", ctypes.c_uint64), ("out_capacity", ctypes.c_uint32),
+                ("height", ctypes.c_int32), ("width", ctypes.c_int32), ("sampling", ctypes.c_int32),
+                ("quant", ctypes.c_uint8 * 2), ("reserved", ctypes.c_uint8 * 6)]
+
+
 # md2_log_panel (csrc/md2hot.hip): new symbols under ABI 24, no version bump
 LOG_COLOR, LOG_WARP, LOG_DISP, LOG_MAP = 0, 1, 2, 3
 LOG_MAX_ITEMS = 4
@@ -319,6 +331,16 @@ def _declare(L):
     L.md2_jpeg_run_indexed.argtypes = [_vp, _vp, ctypes.c_uint64, ctypes.POINTER(JpegImage),
                                        ctypes.POINTER(ctypes.c_uint64), ctypes.c_int, ctypes.POINTER(JpegBank), _vp,
                                        ctypes.c_uint64, _vp, _vp]
+    L.md2_jpeg_encode_bound.restype = ctypes.c_size_t
+    L.md2_jpeg_encode_bound.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    L.md2_jpeg_encode_workspace_bytes.restype = ctypes.c_size_t
+    L.md2_jpeg_encode_workspace_bytes.argtypes = [ctypes.POINTER(JpegEncImage), ctypes.c_int]
+    L.md2_jpeg_encode_check.restype = ctypes.c_int
+    L.md2_jpeg_encode_check.argtypes = [ctypes.POINTER(JpegEncImage), ctypes.c_int, ctypes.c_int, ctypes.c_uint64,
+                                        ctypes.c_uint64]
+    L.md2_jpeg_encode.restype = ctypes.c_int
+    L.md2_jpeg_encode.argtypes = [_vp, ctypes.c_uint64, ctypes.POINTER(JpegEncImage), _vp, ctypes.c_int, _vp,
+                                  ctypes.c_int, _vp, ctypes.c_uint64, _vp, ctypes.c_size_t, _vp, _vp, _vp]
     L.md2_depth_export16.restype = ctypes.c_int
     L.md2_depth_export16.argtypes = [ctypes.POINTER(Depth16Desc)] + [_vp] * 4
     L.md2_depth_export16_check.restype = ctypes.c_int

@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB_NAME = "libmd2hot.so"
 LIB_PATH = os.path.join(CSRC, LIB_NAME)
-SOURCES = ["md2hot.hip", "decoder.hip", "pose.hip", "augment.hip", "bnorm.hip", "pool.hip", "adam.hip", "disphead.hip", "stem.hip", "bias_act.hip", "conv.hip", "direct.hip", "glue.hip", "eval.hip", "velo.hip", "traj.hip", "viz.hip", "jpeg.hip", "points.hip"]
+SOURCES = ["md2hot.hip", "decoder.hip", "pose.hip", "augment.hip", "bnorm.hip", "pool.hip", "adam.hip", "disphead.hip", "stem.hip", "bias_act.hip", "conv.hip", "direct.hip", "glue.hip", "eval.hip", "velo.hip", "traj.hip", "viz.hip", "jpeg.hip", "points.hip", "jpegenc.hip"]
 HEADERS = [os.path.join(INCLUDE, "md2hot.h"), os.path.join(CSRC, "md2_bf16.h"), os.path.join(CSRC, "md2_bn_expr.h"),
            os.path.join(CSRC, "md2_x6.h")]
 ARCH = os.environ.get("MD2_OFFLOAD_ARCH", "gfx950")

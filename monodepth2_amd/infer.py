@@ -11,6 +11,9 @@ to the original image size.  The networks run through `evaluate_depth.predict_di
 (eval mode, no_grad); the picture — resize, 95th percentile, minimum, Normalize, colormap,
 uint8, numpy and matplotlib per image on the host in the reference — is the fused HIP
 operator of `viz_ops.colorize_disparity`, one call per group of equally sized originals.
+NAME_disp.jpeg is encoded on the device from the picture left there (csrc/jpegenc.hip,
+quality 75 and 4:2:0, Pillow's defaults): the file is byte-equal to what
+`pil.fromarray(picture).save(path)` writes, and no full-size picture is copied to the host.
 
 The feed-size LANCZOS resize and ToTensor (test_simple.py:125-128) run on the device too,
 through a one-frame, one-scale `GpuAugment` plan without flip or colour jitter, cached per
@@ -34,6 +37,7 @@ import torch
 from . import networks
 from .augment import GpuAugment, ItemDraw, pack_items
 from .evaluate_depth import STEREO_SCALE_FACTOR, predict_disparities
+from .jpeg_ops import encode_jpeg_batch, jpeg_file_bytes
 from .layers import disp_to_depth
 from .viz_ops import colorize_disparity
 
@@ -89,15 +93,9 @@ def preprocess(image, feed_hw: Sequence[int], device="cuda") -> torch.Tensor:
     return color[0][0]
 
 
-def predict_images(encoder, depth_decoder, images: Sequence, feed_hw: Sequence[int],
-                   pred_metric_depth: bool = False) -> List[Tuple[np.ndarray, np.ndarray]]:
-    """test_simple.py:124-155 for a list of images (PIL images or (H,W,3) uint8 arrays, any
-    sizes).  Returns per image (saved, picture): the (1,1,h,w) float32 array the reference
-    saves — the scaled disparity, or STEREO_SCALE_FACTOR * depth with `pred_metric_depth` —
-    and the (H,W,3) uint8 magma picture at the image's own size.  Images of equal original
-    size share one colorize_disparity call; one device-to-host copy per group at the end."""
-    if not images:
-        return []
+def _predict(encoder, depth_decoder, images: Sequence, feed_hw: Sequence[int], pred_metric_depth: bool):
+    """The shared part of predict_images and predict_files: (PIL images, saved arrays, groups),
+    groups a list of (indices, (n, H, W, 3) uint8 device pictures) per original size."""
     if feed_hw[0] % 32 or feed_hw[1] % 32 or min(feed_hw) < 64:
         # the encoder halves five times and the decoder's ReflectionPad2d(1) needs 2 x 2 there
         raise ValueError("the feed size must be a multiple of 32 and at least 64 x 64, got {} x {}".format(*feed_hw))
@@ -110,13 +108,56 @@ def predict_images(encoder, depth_decoder, images: Sequence, feed_hw: Sequence[i
     groups: Dict[tuple, List[int]] = {}
     for i, im in enumerate(images):
         groups.setdefault((im.height, im.width), []).append(i)
-    pictures = [None] * len(images)
+    pictures = []
     for size, idx in groups.items():
         sel = torch.as_tensor(idx, device=device)
-        rgb = colorize_disparity(disp[sel] if len(idx) != len(images) else disp, size).cpu().numpy()
+        pictures.append((idx, colorize_disparity(disp[sel] if len(idx) != len(images) else disp, size)))
+    return images, saved, pictures
+
+
+def predict_images(encoder, depth_decoder, images: Sequence, feed_hw: Sequence[int],
+                   pred_metric_depth: bool = False) -> List[Tuple[np.ndarray, np.ndarray]]:
+    """test_simple.py:124-155 for a list of images (PIL images or (H,W,3) uint8 arrays, any
+    sizes).  Returns per image (saved, picture): the (1,1,h,w) float32 array the reference
+    saves — the scaled disparity, or STEREO_SCALE_FACTOR * depth with `pred_metric_depth` —
+    and the (H,W,3) uint8 magma picture at the image's own size.  Images of equal original
+    size share one colorize_disparity call; one device-to-host copy per group at the end."""
+    if not images:
+        return []
+    images, saved, groups = _predict(encoder, depth_decoder, images, feed_hw, pred_metric_depth)
+    pictures = [None] * len(images)
+    for idx, rgb in groups:
+        rgb = rgb.cpu().numpy()
         for j, i in enumerate(idx):
             pictures[i] = rgb[j]
     return [(saved[i:i + 1], pictures[i]) for i in range(len(images))]
+
+
+def predict_files(encoder, depth_decoder, images: Sequence, feed_hw: Sequence[int],
+                  pred_metric_depth: bool = False) -> List[Tuple[np.ndarray, bytes]]:
+    """predict_images for writing: per image (saved, jpeg), jpeg the bytes of NAME_disp.jpeg.
+    The pictures stay where the colour-map chain left them and are encoded there
+    (jpeg_ops.encode_jpeg_batch, one call for the whole list) with Pillow's defaults, quality
+    75 and 4:2:0; only the compressed streams come back.  Every file is byte-equal to
+    `pil.fromarray(picture).save(path)` of predict_images' picture."""
+    if not images:
+        return []
+    images, saved, groups = _predict(encoder, depth_decoder, images, feed_hw, pred_metric_depth)
+    order, offsets, sizes, pos = [], [], [], 0
+    for idx, rgb in groups:
+        n, h, w, _ = rgb.shape
+        for j, i in enumerate(idx):
+            order.append(i)
+            offsets.append(pos + j * h * w * 3)
+            sizes.append((h, w))
+        pos += n * h * w * 3
+    flat = groups[0][1].reshape(-1) if len(groups) == 1 else torch.cat([rgb.reshape(-1) for _, rgb in groups])
+    streams = encode_jpeg_batch(flat.contiguous(), quality=75, sampling="4:2:0", device=flat.device, check=True,
+                                offsets=offsets, sizes=sizes)
+    files = [None] * len(images)
+    for i, s in zip(order, streams):
+        files[i] = jpeg_file_bytes(s)
+    return [(saved[i:i + 1], files[i]) for i in range(len(images))]
 
 
 def parse_args(argv=None):
@@ -158,14 +199,15 @@ def main(argv=None):
     todo = [(i, p) for i, p in enumerate(paths) if not p.endswith("_disp.jpg")]   # never a picture of a picture
     for start in range(0, len(todo), BATCH):
         chunk = todo[start:start + BATCH]
-        results = predict_images(encoder, depth_decoder, [pil.open(p).convert("RGB") for _, p in chunk], feed_hw,
-                                 args.pred_metric_depth)
+        results = predict_files(encoder, depth_decoder, [pil.open(p).convert("RGB") for _, p in chunk], feed_hw,
+                                args.pred_metric_depth)
         for (idx, path), (saved, picture) in zip(chunk, results):
             name = os.path.splitext(os.path.basename(path))[0]
             npy = os.path.join(output_directory, "{}_{}.npy".format(name, "depth" if args.pred_metric_depth else "disp"))
             np.save(npy, saved)
             jpeg = os.path.join(output_directory, "{}_disp.jpeg".format(name))
-            pil.fromarray(picture).save(jpeg)
+            with open(jpeg, "wb") as f:
+                f.write(picture)
             print("   Processed {:d} of {:d} images - saved predictions to:".format(idx + 1, len(paths)))
             print("   - {}".format(jpeg))
             print("   - {}".format(npy))

@@ -10,6 +10,13 @@ segments of a batch with their (deduplicated) tables in one pinned block and run
 decoder: frame i lands in `out` as a tight (h, w, 3) image at byte `offsets[i]`, every byte
 equal to `np.asarray(Image.open(path).convert("RGB"))`.  There is no CPU path: a non-CUDA
 device is an error.
+
+The other direction (csrc/jpegenc.hip, `md2_jpeg_encode`): `encode_jpeg_batch(frames,
+quality, sampling)` encodes RGB frames of mixed sizes on the device and returns JpegStreams
+with the quality's tables (`quality_tables`) and the standard Huffman tables, which the
+decoder, the indexer and a pack take as they are; `jpeg_file_bytes(stream)` writes the file
+around a stream on the host.  Every byte is what Pillow's `save(quality=, subsampling=)`
+writes for the frame.
 """
 from __future__ import annotations
 
@@ -558,3 +565,270 @@ def decode_jpeg_batch_indexed(streams: Sequence[JpegStream], indexes: Sequence[n
                 raise RuntimeError(f"decode_jpeg_batch_indexed: stream index {bad[0]} did not decode "
                                    f"(status {int(status[bad[0]])}); bad indices {bad}")
     return status
+
+
+# ------------------------------------------------------------------ encoding (csrc/jpegenc.hip)
+# The base quantisation tables of ITU-T T.81 Annex K (K.1 luma, K.2 chroma), natural order.
+BASE_LUMA = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56,
+             14, 17, 22, 29, 51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92,
+             49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99)
+BASE_CHROMA = (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99,
+               47, 66, 99, 99, 99, 99, 99, 99) + (99,) * 32
+
+# The four Huffman tables of Annex K (K.3 to K.6) as a DHT segment lists them: the only ones
+# the encoder writes.  {(class, id): (counts[16], values)}, class 0 = DC, id 0 = luma.
+STD_HUFF = {
+    (0, 0): ((0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0), bytes(range(12))),
+    (0, 1): ((0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0), bytes(range(12))),
+    (1, 0): ((0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125), bytes.fromhex(
+        "01020300041105122131410613516107227114328191a1082342b1c11552d1f02433627282090a161718191a25262728292a34"
+        "35363738393a434445464748494a535455565758595a636465666768696a737475767778797a838485868788898a9293949596"
+        "9798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae1e2e3e4e5e6e7e8e9eaf1"
+        "f2f3f4f5f6f7f8f9fa")),
+    (1, 1): ((0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119), bytes.fromhex(
+        "000102031104052131061241510761711322328108144291a1b1c109233352f0156272d10a162434e125f11718191a26272829"
+        "2a35363738393a434445464748494a535455565758595a636465666768696a737475767778797a82838485868788898a929394"
+        "95969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae2e3e4e5e6e7e8e9ea"
+        "f2f3f4f5f6f7f8f9fa")),
+}
+
+SAMPLING_NAMES = {"4:4:4": _lib.JPEG_444, "444": _lib.JPEG_444, "4:2:2": _lib.JPEG_422, "422": _lib.JPEG_422,
+                  "4:2:0": _lib.JPEG_420, "420": _lib.JPEG_420}
+_FACTORS = {v: k for k, v in SAMPLINGS.items()}
+
+
+def sampling_class(sampling) -> int:
+    """JPEG_444 / 422 / 420 from "4:2:0", "420", 420 or the class itself."""
+    if isinstance(sampling, int) and sampling in _FACTORS:
+        return sampling
+    try:
+        return SAMPLING_NAMES[str(sampling)]
+    except KeyError:
+        raise ValueError(f"unknown sampling {sampling!r} (4:4:4, 4:2:2 or 4:2:0)") from None
+
+
+def quality_tables(quality: int) -> Tuple[Tuple[int, ...], Tuple[int, ...]]:
+    """(luma, chroma) quantisation tables of a quality 1..100 as libjpeg makes them, natural
+    order: the base tables scaled by 5000 / quality below 50 and 200 - 2 quality from 50 on,
+    (base * scale + 50) / 100 clipped to 1..255."""
+    quality = int(quality)
+    if not 1 <= quality <= 100:
+        raise ValueError(f"quality {quality} outside 1..100")
+    scale = 5000 // quality if quality < 50 else 200 - 2 * quality
+    return tuple(tuple(min(max((b * scale + 50) // 100, 1), 255) for b in base) for base in (BASE_LUMA, BASE_CHROMA))
+
+
+def _segment(marker: int, payload: bytes) -> bytes:
+    return struct.pack(">BBH", 0xFF, marker, len(payload) + 2) + payload
+
+
+def jpeg_file_bytes(stream: JpegStream) -> bytes:
+    """The JFIF file of a stream, written as Pillow (libjpeg) writes one: SOI, APP0 JFIF 1.01
+    (no units, density 1 x 1), DQT 0 and 1 in zigzag order, SOF0 (components 1, 2, 3, tables
+    0, 1, 1), DHT DC0, AC0, DC1, AC1, SOS, the data with every FF stuffed to FF 00, EOI.  Host
+    only.  A stream this layout cannot hold is refused: luma factors other than 1x1 / 2x1 /
+    2x2 over 1x1 chroma, or chroma components with different tables."""
+    factors = tuple(tuple(f) for f in stream.factors)
+    if factors not in SAMPLINGS:
+        raise ValueError(f"jpeg_file_bytes: sampling factors {factors} (luma 1x1, 2x1 or 2x2 over 1x1 chroma)")
+    quant = [tuple(int(v) for v in q) for q in stream.quant]
+    if quant[1] != quant[2]:
+        raise ValueError("jpeg_file_bytes: the chroma components use different quantisation tables")
+    tabs = []
+    for cls, ids in ((0, stream.dc), (1, stream.ac)):
+        if stream.huff[(cls, ids[1])] != stream.huff[(cls, ids[2])]:
+            raise ValueError("jpeg_file_bytes: the chroma components use different Huffman tables")
+        tabs.append([stream.huff[(cls, ids[0])], stream.huff[(cls, ids[1])]])
+    if any(len(q) != 64 or min(q) < 1 or max(q) > 255 for q in quant):
+        raise ValueError("jpeg_file_bytes: a quantisation table is not 64 values of 1..255")
+    out = [b"\xff\xd8", _segment(0xE0, b"JFIF\0" + struct.pack(">BBBHHBB", 1, 1, 0, 1, 1, 0, 0))]
+    for tid, q in ((0, quant[0]), (1, quant[1])):
+        out.append(_segment(0xDB, bytes([tid]) + bytes(q[ZIGZAG[k]] for k in range(64))))
+    sof = struct.pack(">BHHB", 8, stream.height, stream.width, 3)
+    for c in range(3):
+        sof += bytes([c + 1, factors[c][0] << 4 | factors[c][1], 0 if c == 0 else 1])
+    out.append(_segment(0xC0, sof))
+    for tid in (0, 1):
+        for cls in (0, 1):
+            counts, vals = tabs[cls][tid]
+            out.append(_segment(0xC4, bytes([cls << 4 | tid]) + bytes(counts) + bytes(vals)))
+    out.append(_segment(0xDA, b"\x03\x01\x00\x02\x11\x03\x11\x00\x3f\x00"))
+    out.append(bytes(stream.data).replace(b"\xff", b"\xff\x00"))
+    out.append(b"\xff\xd9")
+    return b"".join(out)
+
+
+def standard_stream(height: int, width: int, sampling: int, quality: int, data: bytes) -> JpegStream:
+    """The JpegStream of an encoded frame: the quality's tables, the standard Huffman tables."""
+    luma, chroma = quality_tables(quality)
+    return JpegStream(height, width, sampling, _FACTORS[sampling], (luma, chroma, chroma), dict(STD_HUFF),
+                      (0, 1, 1), (0, 1, 1), data)
+
+
+def _per_image(value, n: int, what: str) -> list:
+    if isinstance(value, (list, tuple)):
+        if len(value) != n:
+            raise ValueError(f"{len(value)} {what} values for {n} frames")
+        return list(value)
+    return [value] * n
+
+
+def encode_bound(height: int, width: int, sampling: int) -> int:
+    """md2_jpeg_encode_bound: a capacity no stream of that geometry exceeds (208 bytes per block)."""
+    need = _lib.lib().md2_jpeg_encode_bound(int(height), int(width), int(sampling))
+    if need == 0:
+        _lib.check(-1, "md2_jpeg_encode_bound")
+    return need
+
+
+def describe_encode(shapes: Sequence[Tuple[int, int]], samplings: Sequence[int], qualities: Sequence[int],
+                    in_offsets: Sequence[int], out_offsets: Optional[Sequence[int]] = None,
+                    capacities: Optional[Sequence[int]] = None):
+    """The host side of an encode call: the md2_jpegenc_image array, the deduplicated bank of
+    quantisation tables (natural order) and the bytes of `out` the ranges need: (images,
+    quant_tables, out_bytes).  Without out_offsets every image gets md2_jpeg_encode_bound
+    bytes at the next multiple of 16."""
+    n = len(shapes)
+    images = (_lib.JpegEncImage * max(n, 1))()
+    quant: Dict[Tuple[int, ...], int] = {}
+    pos = 0
+    for i, (h, w) in enumerate(shapes):
+        im = images[i]
+        im.height, im.width, im.sampling = int(h), int(w), int(samplings[i])
+        im.in_offset = int(in_offsets[i])
+        luma, chroma = quality_tables(qualities[i])
+        im.quant[0] = quant.setdefault(luma, len(quant))
+        im.quant[1] = quant.setdefault(chroma, len(quant))
+        if out_offsets is None:
+            im.out_offset, im.out_capacity = pos, encode_bound(h, w, im.sampling)
+        else:
+            im.out_offset, im.out_capacity = int(out_offsets[i]), int(capacities[i])
+        pos = max(pos, _align(im.out_offset + im.out_capacity, 16))
+    if len(quant) > 256:
+        raise ValueError("more than 256 distinct quantisation tables in one batch: encode it in parts")
+    return images, list(quant), max(pos, 16)
+
+
+def check_encode(images, n: int, num_quant: int, in_bytes: int, out_bytes: int):
+    """md2_jpeg_encode's argument checks alone (host only): raises what it would refuse."""
+    _lib.check(_lib.lib().md2_jpeg_encode_check(images, n, num_quant, in_bytes, out_bytes), "md2_jpeg_encode_check")
+
+
+def encode_tables_bytes(n: int, num_quant: int) -> int:
+    """Bytes of the block run_encode reads its tables from: the image array, then the bank."""
+    return _align(n * ctypes.sizeof(_lib.JpegEncImage), 16) + num_quant * _lib.JPEG_QUANT_BYTES
+
+
+def fill_encode_tables(host: np.ndarray, images, n: int, quant):
+    """The image array and the quantisation bank written into `host` (uint8) in
+    encode_tables_bytes's layout."""
+    nb = n * ctypes.sizeof(_lib.JpegEncImage)
+    host[:nb] = np.frombuffer(images, np.uint8, nb)
+    q0 = _align(nb, 16)
+    host[nb:q0] = 0
+    host[q0:q0 + len(quant) * _lib.JPEG_QUANT_BYTES] = np.asarray(quant, dtype=np.uint16).reshape(-1).view(np.uint8)
+
+
+def run_encode(tables: torch.Tensor, frames: torch.Tensor, images, n: int, num_quant: int, out: torch.Tensor,
+               device: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The launches of an encode call whose tables (fill_encode_tables's bytes, 16-byte aligned)
+    and frames are on the device or on their way there on the current stream.  Returns
+    (stream_bytes, status), uint32 values in int32 tensors of n on the device."""
+    L = _lib.lib()
+    need = L.md2_jpeg_encode_workspace_bytes(images, n)
+    if need == 0:
+        _lib.check(-1, "md2_jpeg_encode_workspace_bytes")
+    with torch.cuda.device(device):
+        workspace = torch.empty(need, dtype=torch.uint8, device=device)
+        result = torch.empty((2, n), dtype=torch.int32, device=device)
+        q0 = _align(n * ctypes.sizeof(_lib.JpegEncImage), 16)
+        _lib.check(L.md2_jpeg_encode(frames.data_ptr(), frames.numel(), images, tables.data_ptr(), n,
+                                     tables.data_ptr() + q0, num_quant, out.data_ptr(), out.numel(),
+                                     workspace.data_ptr(), need, result[0].data_ptr(), result[1].data_ptr(),
+                                     _lib.stream(device)), "md2_jpeg_encode")
+    return result[0], result[1]
+
+
+def encode_jpeg_batch(frames, quality=92, sampling="4:2:0", device=None, check: bool = False, offsets=None,
+                      sizes=None, fill=None, pool=None) -> List[JpegStream]:
+    """Encodes a batch of RGB frames as baseline JPEG on the device (md2_jpeg_encode): every
+    stream's data, tables and jpeg_file_bytes output are what Pillow's save(quality=...,
+    subsampling=...) writes for the frame.  `frames`: a list of (h, w, 3) uint8 arrays or
+    tensors of mixed sizes, or one flat uint8 device tensor with `offsets` (bytes) and `sizes`
+    ((h, w) each) of the tight frames in it.  quality and sampling: one value, or one per
+    frame.  Host frames travel in one pinned block with the tables (one upload); then the
+    launches; then the lengths and status words come back, and the streams in one copy of
+    exactly their bytes.  The streams carry the quality's tables and the standard Huffman
+    tables, so decode_jpeg_batch, index_jpeg_batch and pack records take them as they are.
+    check=True raises a RuntimeError naming the first frame whose status is not 0 (such a
+    stream has empty data).  With `fill`, `frames` is a list of (h, w) sizes and fill(i, dest)
+    writes frame i into dest, an (h, w, 3) uint8 view of the pinned block (through pool.map if
+    a thread pool is given): a decoder's output lands in pinned memory without a copy of the
+    list.  There is no CPU path."""
+    device = _cuda_device(device, "encode_jpeg_batch")
+    flat = torch.is_tensor(frames) and offsets is not None
+    if flat:
+        if sizes is None or len(sizes) != len(offsets):
+            raise ValueError("a flat frame buffer needs as many sizes as offsets")
+        if not frames.is_cuda or frames.dtype != torch.uint8 or frames.dim() != 1 or not frames.is_contiguous():
+            raise ValueError("a flat frame buffer must be a contiguous 1-D uint8 device tensor")
+        shapes = [(int(h), int(w)) for h, w in sizes]
+        in_offsets = [int(o) for o in offsets]
+        arrays = None
+    elif fill is not None:
+        arrays = None
+        shapes = [(int(h), int(w)) for h, w in frames]
+    else:
+        arrays = []
+        for f in frames:
+            a = f.detach().cpu().numpy() if torch.is_tensor(f) else np.asarray(f)
+            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError(f"a frame must be (h, w, 3) uint8, not {a.dtype} {a.shape}")
+            arrays.append(np.ascontiguousarray(a))
+        shapes = [a.shape[:2] for a in arrays]
+    n = len(shapes)
+    if n == 0:
+        return []
+    samplings = [sampling_class(s) for s in _per_image(sampling, n, "sampling")]
+    qualities = [int(q) for q in _per_image(quality, n, "quality")]
+    tables_bytes = _align(encode_tables_bytes(n, 2 * n), 16)   # room for every table before they are deduplicated
+    if not flat:
+        in_offsets, pos = [], 0
+        for h, w in shapes:
+            in_offsets.append(pos)
+            pos += _align(h * w * 3, 16)
+        frames_bytes = max(pos, 16)
+    images, quant, out_bytes = describe_encode(shapes, samplings, qualities, in_offsets)
+    with torch.cuda.device(device):
+        total = tables_bytes + (0 if flat else frames_bytes)
+        pinned = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+        host = pinned.numpy()
+        fill_encode_tables(host, images, n, quant)
+        if fill is not None:
+            def one(i):
+                h, w = shapes[i]
+                o = tables_bytes + in_offsets[i]
+                fill(i, host[o:o + h * w * 3].reshape(h, w, 3))
+            list(pool.map(one, range(n)) if pool is not None else map(one, range(n)))
+        elif not flat:
+            for a, o in zip(arrays, in_offsets):
+                host[tables_bytes + o:tables_bytes + o + a.size] = a.reshape(-1)
+        staged = torch.empty(total, dtype=torch.uint8, device=device)
+        staged.copy_(pinned, non_blocking=True)
+        source = frames if flat else staged[tables_bytes:]
+        check_encode(images, n, len(quant), source.numel(), out_bytes)
+        out = torch.empty(out_bytes, dtype=torch.uint8, device=device)
+        lengths, status = run_encode(staged, source, images, n, len(quant), out, device)
+        result = torch.stack([lengths, status]).cpu().numpy().astype(np.int64) & 0xFFFFFFFF   # waits for the launches
+        lens = [0 if result[1, i] else int(result[0, i]) for i in range(n)]
+        bad = np.flatnonzero(result[1]).tolist()
+        if check and bad:
+            raise RuntimeError(f"encode_jpeg_batch: frame index {bad[0]} did not encode (status "
+                               f"{int(result[1, bad[0]])}); bad indices {bad}")
+        parts = [out[images[i].out_offset:images[i].out_offset + lens[i]] for i in range(n)]
+        data = torch.cat(parts).cpu().numpy().tobytes()
+    streams, pos = [], 0
+    for i in range(n):
+        streams.append(standard_stream(shapes[i][0], shapes[i][1], samplings[i], qualities[i], data[pos:pos + lens[i]]))
+        pos += lens[i]
+    return streams

@@ -7,7 +7,12 @@ the device decoder needs with no further host work: the unstuffed entropy-coded 
 synchronisation index (jpeg_ops.index_jpeg_batch: the entry state of every 1024-bit
 subsequence, found once on the device) directly behind it.  A file the device decoder does
 not take (PNG, progressive, ...) is stored as its PIL-decoded RGB bytes, kind RAW, so a
-batch from the pack is always bit-equal to the same batch from disk.  `FramePack` opens such
+batch from the pack is always bit-equal to the same batch from disk.  With `transcode=(quality,
+sampling)` such a file is instead encoded as baseline JPEG on the device (jpeg_ops.
+encode_jpeg_batch) and stored as a JPEG record under its own key: a fraction of the size and
+decoded by the device decoder like the rest, but lossy; a batch from such a pack is bit-equal
+to the batch from the tree after `convert_dataset` with the same quality and sampling, read
+as .jpg with --device_decode.  `FramePack` opens such
 a file; `loader.BatchLoader(pack=...)` then feeds the step with an index lookup and one
 `os.preadv` per frame, straight into pinned memory.
 
@@ -25,7 +30,9 @@ last, so a build that died leaves no magic):
   huff      num_huff tables of 16 counts + 256 values     } a batch's bank is a gather by id
   records   num_records x 96 bytes, sorted by name: u32 kind (0 JPEG, 1 RAW), height, width,
             sampling; u64 data_offset, data_bytes; u32 stream_bytes, name_offset, name_bytes;
-            u32 quant[3], dc[3], ac[3] (table ids); zeros
+            u32 quant[3], dc[3], ac[3] (table ids); 16 reserved bytes: byte 0 = 1 and byte
+            1 = the quality for a frame transcoded from a lossless file, else zeros (readers
+            ignore them when decoding)
   names     the keys, UTF-8, back to back: a frame's path relative to --data_path with "/"
 
 Equal tables are stored once; files written with optimised coding carry their own, so the
@@ -74,10 +81,11 @@ def frame_key(path: str, data_path: str) -> str:
 class PackRecord:
     """One frame on its way into a pack.  JPEG: `stream` (a jpeg_ops.JpegStream) and `index`
     (its index bytes, jpeg_ops.index_jpeg_batch's or pack_index's).  RAW: `raw`, the decoded
-    (h, w, 3) uint8 RGB frame."""
-    __slots__ = ("name", "stream", "index", "raw")
+    (h, w, 3) uint8 RGB frame.  `transcoded`: the quality a lossless file was encoded with on
+    its way in (0: the stream is the file's own)."""
+    __slots__ = ("name", "stream", "index", "raw", "transcoded")
 
-    def __init__(self, name: str, stream=None, index=None, raw=None):
+    def __init__(self, name: str, stream=None, index=None, raw=None, transcoded: int = 0):
         if (stream is None) == (raw is None):
             raise ValueError(f"{name}: a record is either a stream with its index or raw RGB")
         if stream is not None:
@@ -89,7 +97,9 @@ class PackRecord:
             raw = np.ascontiguousarray(raw, dtype=np.uint8)
             if raw.ndim != 3 or raw.shape[2] != 3:
                 raise ValueError(f"{name}: raw frames are (h, w, 3) uint8, not {raw.shape}")
-        self.name, self.stream, self.index, self.raw = name, stream, index, raw
+        if transcoded and (stream is None or not 1 <= int(transcoded) <= 100):
+            raise ValueError(f"{name}: a transcoded record is a stream with its quality, 1..100")
+        self.name, self.stream, self.index, self.raw, self.transcoded = name, stream, index, raw, int(transcoded)
 
 
 def _huff_bytes(counts, vals) -> bytes:
@@ -121,21 +131,24 @@ def write_pack(path: str, records: Iterable[PackRecord]) -> int:
                 q = [quant.setdefault(np.asarray(s.quant[c], dtype="<u2").tobytes(), len(quant)) for c in range(3)]
                 dc = [huff.setdefault(_huff_bytes(*s.huff[(0, s.dc[c])]), len(huff)) for c in range(3)]
                 ac = [huff.setdefault(_huff_bytes(*s.huff[(1, s.ac[c])]), len(huff)) for c in range(3)]
-                rows.append((rec.name, KIND_JPEG, s.height, s.width, s.sampling, pos, nbytes, len(s.data), q, dc, ac))
+                rows.append((rec.name, KIND_JPEG, s.height, s.width, s.sampling, pos, nbytes, len(s.data), q, dc, ac,
+                             rec.transcoded))
             else:
                 h, w = rec.raw.shape[:2]
                 f.write(rec.raw.tobytes())
                 nbytes = _align16(h * w * 3)
                 f.write(b"\0" * (nbytes - h * w * 3))
-                rows.append((rec.name, KIND_RAW, h, w, 0, pos, h * w * 3, 0, [0] * 3, [0] * 3, [0] * 3))
+                rows.append((rec.name, KIND_RAW, h, w, 0, pos, h * w * 3, 0, [0] * 3, [0] * 3, [0] * 3, 0))
             pos += nbytes
         rows.sort(key=lambda r: r[0])
         table = np.zeros(len(rows), RECORD)
         names = bytearray()
-        for i, (name, kind, h, w, sampling, off, nbytes, sbytes, q, dc, ac) in enumerate(rows):
+        for i, (name, kind, h, w, sampling, off, nbytes, sbytes, q, dc, ac, transcoded) in enumerate(rows):
             key = name.encode("utf-8")
-            table[i] = (kind, h, w, sampling, off, nbytes, sbytes, len(names), len(key), q, dc, ac,
-                        np.zeros(16, np.uint8))
+            reserved = np.zeros(16, np.uint8)
+            if transcoded:
+                reserved[0], reserved[1] = 1, transcoded
+            table[i] = (kind, h, w, sampling, off, nbytes, sbytes, len(names), len(key), q, dc, ac, reserved)
             names += key
         quant_off = pos
         f.write(b"".join(quant))                      # dicts keep insertion order: id order
@@ -207,6 +220,8 @@ class FramePack:
         self._row = {name: i for i, name in enumerate(self.names)}
         # what the loader asks per frame, as plain Python values
         self._sizes = [(int(h), int(w)) for h, w in zip(r["height"], r["width"])]
+        # frames encoded from lossless files when the pack was built (build_pack's transcode)
+        self.transcoded = int(np.count_nonzero(r["reserved"][:, 0] == 1)) if n else 0
         self._fd = os.open(self.path, os.O_RDONLY)
 
     def __len__(self):
@@ -299,7 +314,14 @@ class FramePack:
 def open_pack(opt) -> Optional[FramePack]:
     """The pack --pack names, or None without the flag."""
     path = getattr(opt, "pack", None)
-    return FramePack(path) if path else None
+    if not path:
+        return None
+    pack = FramePack(path)
+    if pack.transcoded:
+        qualities = sorted({int(q) for q in pack.records["reserved"][pack.records["reserved"][:, 0] == 1, 1]})
+        print(f"{path}: {pack.transcoded} of {len(pack)} frames are lossy JPEG transcodes of PNG files (quality "
+              f"{', '.join(map(str, qualities))}): they decode as the tree would after convert_dataset, not as the PNGs")
+    return pack
 
 
 def frame_paths(data_path: str, line_lists: Sequence[Sequence[str]], dataset: str = "kitti", png: bool = False,
@@ -320,11 +342,13 @@ def frame_paths(data_path: str, line_lists: Sequence[Sequence[str]], dataset: st
     return out
 
 
-def records_from_files(paths: Dict[str, str], device=None, batch: int = 64,
-                       threads: int = 8) -> Iterator[PackRecord]:
+def records_from_files(paths: Dict[str, str], device=None, batch: int = 64, threads: int = 8,
+                       transcode: Optional[Tuple[int, object]] = None) -> Iterator[PackRecord]:
     """The records of the files {key: path}, in key order: read and parsed by `threads` host
     threads, the supported JPEG files indexed on the device `batch` at a time, every other
-    file decoded with PIL into a RAW record."""
+    file decoded with PIL into a RAW record.  transcode=(quality, sampling): such a file is
+    encoded on the device after PIL decoded it, indexed with the rest of its batch and
+    becomes a JPEG record under its own key, marked as transcoded."""
     def load(key):
         path = paths[key]
         try:
@@ -343,28 +367,42 @@ def records_from_files(paths: Dict[str, str], device=None, batch: int = 64,
         for start in range(0, len(keys), batch):
             chunk = keys[start:start + batch]
             got = list(pool.map(load, chunk))
+            encoded = {}
+            if transcode is not None:
+                lossless = [n for n, g in enumerate(got) if not isinstance(g, jpeg_ops.JpegStream)]
+                streams = jpeg_ops.encode_jpeg_batch([got[n] for n in lossless], quality=transcode[0],
+                                                     sampling=transcode[1], device=device, check=True)
+                for n, s in zip(lossless, streams):
+                    got[n] = s
+                    encoded[n] = int(transcode[0])
             on_device = [n for n, g in enumerate(got) if isinstance(g, jpeg_ops.JpegStream)]
             indexes = dict(zip(on_device, jpeg_ops.index_jpeg_batch([got[n] for n in on_device], device)))
             for n, key in enumerate(chunk):
                 if n in indexes:
-                    yield PackRecord(key, stream=got[n], index=indexes[n])
+                    yield PackRecord(key, stream=got[n], index=indexes[n], transcoded=encoded.get(n, 0))
                 else:
                     yield PackRecord(key, raw=got[n])
 
 
 def build_pack(out: str, data_path: str, line_lists: Sequence[Sequence[str]], dataset: str = "kitti",
                png: bool = False, frame_ids: Sequence = (0, -1, 1), use_stereo: bool = False, device=None,
-               batch: int = 64, threads: int = 8) -> Dict:
+               batch: int = 64, threads: int = 8, transcode: Optional[Tuple[int, object]] = None) -> Dict:
     """Parse, index on the device, write: the frames the split lines of `line_lists` name
     under `data_path`, into the pack `out`.  Files are read by `threads` host threads and
-    indexed `batch` at a time.  Returns {"frames", "jpeg", "raw", "pack_bytes", "file_bytes"}
-    (file_bytes: the size of the image files read)."""
+    indexed `batch` at a time.  transcode=(quality, sampling): files the device decoder does
+    not take are encoded as JPEG on the device instead of stored decoded (records_from_files).
+    Returns {"frames", "jpeg", "raw", "transcoded", "pack_bytes", "file_bytes"} (file_bytes:
+    the size of the image files read; transcoded frames count as jpeg too)."""
     paths = frame_paths(data_path, line_lists, dataset, png, frame_ids, use_stereo)
-    stats = {"frames": 0, "jpeg": 0, "raw": 0, "file_bytes": 0}
+    stats = {"frames": 0, "jpeg": 0, "raw": 0, "transcoded": 0, "file_bytes": 0}
+    if transcode is not None:
+        transcode = (int(transcode[0]), jpeg_ops.sampling_class(transcode[1]))
+        jpeg_ops.quality_tables(transcode[0])
 
     def counted():
-        for rec in records_from_files(paths, device, batch, threads):
+        for rec in records_from_files(paths, device, batch, threads, transcode):
             stats["jpeg" if rec.stream is not None else "raw"] += 1
+            stats["transcoded"] += 1 if rec.transcoded else 0
             stats["file_bytes"] += os.path.getsize(paths[rec.name])
             yield rec
 

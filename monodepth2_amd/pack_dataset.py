@@ -4,7 +4,10 @@ train_files.txt val_files.txt ... --out FILE`.
 Reads the split lists, names their frames as `train` / `evaluate_depth` / `evaluate_pose`
 would (--dataset, --png, --frame_ids and --use_stereo as there), and writes the frame pack
 `--pack FILE` of those commands reads (pack.py).  Needs the GPU: the
-synchronisation indexes are computed by the device decoder's own kernel.
+synchronisation indexes are computed by the device decoder's own kernel.  With --png
+--transcode [--quality 92] [--sampling 420] the PNG frames are encoded as JPEG on the device
+(csrc/jpegenc.hip) instead of stored decoded: the pack `convert_dataset` followed by
+`pack_dataset` would give, without writing the .jpg files.
 """
 from __future__ import annotations
 
@@ -25,12 +28,18 @@ def main(argv: Optional[Sequence[str]] = None):
     ap.add_argument("--png", action="store_true", help="the tree holds png files")
     ap.add_argument("--frame_ids", nargs="+", type=int, default=[0, -1, 1])
     ap.add_argument("--use_stereo", action="store_true", help="also pack the other camera of every line")
+    ap.add_argument("--transcode", action="store_true",
+                    help="encode files the device decoder does not take (PNG) as JPEG on the device instead of "
+                         "storing them decoded: a much smaller pack, lossy like convert_dataset")
+    ap.add_argument("--quality", type=int, default=92, help="of --transcode")
+    ap.add_argument("--sampling", default="420", choices=["444", "422", "420"], help="of --transcode")
     ap.add_argument("--batch", type=int, default=64, help="files indexed per device call")
     ap.add_argument("--threads", type=int, default=8, help="host threads reading and parsing files (at most 16)")
     args = ap.parse_args(argv)
     stats = build_pack(args.out, args.data_path, [readlines(p) for p in args.lists], dataset=args.dataset,
                        png=args.png, frame_ids=args.frame_ids, use_stereo=args.use_stereo, batch=args.batch,
-                       threads=min(max(args.threads, 1), 16))
+                       threads=min(max(args.threads, 1), 16),
+                       transcode=(args.quality, args.sampling) if args.transcode else None)
     stats["out"] = args.out
     print(json.dumps(stats))
     return stats
