@@ -1153,6 +1153,65 @@ int md2_jpeg_encode(const uint8_t* in, uint64_t in_bytes, const md2_jpegenc_imag
                     uint32_t* status, void* stream);
 
 /*
+ * 8-bit RGB PNG frames decoded on the device (csrc/png.hip): the last host-side decoder on
+ * the way from a KITTI tree to the training step.  The host reads the chunks, checks their
+ * CRCs and the zlib header (monodepth2_amd/png_ops.py) and uploads, per file, the
+ * concatenated IDAT payload without its 2-byte zlib header: the raw deflate stream followed
+ * by the 4 bytes of the Adler-32 trailer.  The device inflates it (RFC 1951: stored, fixed
+ * and dynamic blocks, every stream zlib's inflate accepts) into the caller's workspace and
+ * then undoes the five scanline filters (bpp = 3) into the tight (height, width, 3) frame,
+ * every byte what Pillow's Image.open(path).convert("RGB") gives; the same pass forms the
+ * Adler-32 of the scanlines and compares it with the trailer.  Integer arithmetic only, no
+ * atomics: two runs are bit-equal.  New symbols under ABI 24, no version bump (as
+ * md2_jpeg_encode).
+ *
+ * streams: device bytes, 16-byte aligned; image i's stream is stream_bytes bytes at
+ * stream_offset (a multiple of 16).  images: HOST array of n, read for the checks and the
+ * launch sizes only; dev_images: a DEVICE copy of it (8-byte aligned), which the kernels
+ * read, so the caller uploads it with the streams and the call stages nothing.  workspace:
+ * device bytes, 16-byte aligned, md2_png_workspace_bytes of the batch (the inflated
+ * scanlines, height * (1 + 3 width) bytes per image rounded up to 16), no initialisation
+ * needed.  out: device bytes; frame i is written at out_offset (a multiple of 16) and no
+ * other byte of out is.  status: device uint32[n], written by the call: 0, or
+ * MD2_PNG_ST_* bits.  Decoding stops at the image's last byte, so stream bytes after a
+ * complete image set no bit (Pillow ignores them too).  With a bit of the inflate stage set
+ * (BLOCK, CODE, END, DIST) the frame is not written at all; with FILTER or ADLER alone it is
+ * written (a row with a bad filter byte as if its filter were None).  A corrupt stream writes
+ * nothing outside its own workspace range and its own status word, and the other images of
+ * the batch are unaffected.
+ *
+ * Two launches on `stream` (inflate: one wave per stream; unfilter + Adler-32: one wave per
+ * image), no allocation, no host synchronisation, hipGraph-capturable.  Refused
+ * (MD2_ERR_ARG) before anything is launched: n outside 0..4096, NULL arguments, a height or
+ * width outside 1..8192, a stream_offset or out_offset that is no multiple of 16, a stream
+ * that leaves streams_bytes, a frame that leaves out_bytes, misaligned buffers, a workspace
+ * that is too small.  md2_png_check runs the checks that need no pointer alone (host only,
+ * launches nothing).  md2_png_workspace_bytes: 0 (and md2_last_error) for a geometry the
+ * decoder refuses.
+ */
+#define MD2_PNG_ST_BLOCK  (1u << 0)  /* block type 3, or a stored block whose LEN and NLEN disagree */
+#define MD2_PNG_ST_CODE   (1u << 1)  /* a code-length set zlib's inflate refuses, a bit pattern that is no code,
+                                        literal/length symbols 286/287, distance symbols 30/31 */
+#define MD2_PNG_ST_END    (1u << 2)  /* the stream ends before the image is complete */
+#define MD2_PNG_ST_DIST   (1u << 3)  /* a distance reaching before the first output byte */
+#define MD2_PNG_ST_FILTER (1u << 4)  /* a row's filter byte above 4 */
+#define MD2_PNG_ST_ADLER  (1u << 5)  /* the trailer is not the Adler-32 of the h * (1 + 3w) raw bytes */
+
+typedef struct md2_png_image {
+    int32_t height, width;          /* 1..8192 */
+    uint64_t out_offset;            /* bytes into out, a multiple of 16: the tight (height, width, 3) frame */
+    uint64_t stream_offset;         /* bytes into streams, a multiple of 16 */
+    uint32_t stream_bytes;          /* the deflate stream and the 4 trailer bytes */
+    uint32_t reserved;              /* 0; the struct is 32 bytes */
+} md2_png_image;
+
+size_t md2_png_workspace_bytes(const md2_png_image* images, int n);
+int md2_png_check(const md2_png_image* images, int n, uint64_t streams_bytes, uint64_t out_bytes);
+int md2_png_run(const uint8_t* streams, uint64_t streams_bytes, const md2_png_image* images,
+                const md2_png_image* dev_images, int n, uint8_t* workspace, size_t workspace_bytes, uint8_t* out,
+                uint64_t out_bytes, uint32_t* status, void* stream);
+
+/*
  * The training log's pictures (csrc/md2hot.hip): what the reference's Trainer.log writes at
  * a log step (trainer.py:540-572, with normalize_image, utils.py:22-28) for the first
  * `items` images of the batch, as one uint8 contact sheet (items, sheet_h, sheet_w, 3) filled

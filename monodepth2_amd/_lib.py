@@ -82,6 +82,7 @@ EXPORTS = ["md2_abi_version", "md2_last_error", "md2_workspace_bytes", "md2_sele
            "md2_jpeg_run",
            "md2_jpeg_index_bytes", "md2_jpeg_index", "md2_jpeg_check_indexed", "md2_jpeg_run_indexed",
            "md2_jpeg_encode_bound", "md2_jpeg_encode_workspace_bytes", "md2_jpeg_encode_check", "md2_jpeg_encode",
+           "md2_png_workspace_bytes", "md2_png_check", "md2_png_run",
            "md2_log_panel_tile_blocks", "md2_log_panel_check", "md2_log_panel_workspace_bytes", "md2_log_panel",
            "md2_depth_points", "md2_depth_points_workspace_bytes"]
 
@@ -264,6 +265,15 @@ class JpegEncImage(ctypes.Structure):
                 ("quant", ctypes.c_uint8 * 2), ("reserved", ctypes.c_uint8 * 6)]
 
 
+# md2_png_run (csrc/png.hip): new symbols under ABI 24, no version bump
+PNG_ST_BLOCK, PNG_ST_CODE, PNG_ST_END, PNG_ST_DIST, PNG_ST_FILTER, PNG_ST_ADLER = 1, 2, 4, 8, 16, 32
+
+
+class PngImage(ctypes.Structure):
+    _fields_ = [("height", ctypes.c_int32), ("width", ctypes.c_int32), ("out_offset", ctypes.c_uint64),
+                ("stream_offset", ctypes.c_uint64), ("stream_bytes", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
 # md2_log_panel (csrc/md2hot.hip): new symbols under ABI 24, no version bump
 LOG_COLOR, LOG_WARP, LOG_DISP, LOG_MAP = 0, 1, 2, 3
 LOG_MAX_ITEMS = 4
@@ -341,6 +351,13 @@ def _declare(L):
     L.md2_jpeg_encode.restype = ctypes.c_int
     L.md2_jpeg_encode.argtypes = [_vp, ctypes.c_uint64, ctypes.POINTER(JpegEncImage), _vp, ctypes.c_int, _vp,
                                   ctypes.c_int, _vp, ctypes.c_uint64, _vp, ctypes.c_size_t, _vp, _vp, _vp]
+    L.md2_png_workspace_bytes.restype = ctypes.c_size_t
+    L.md2_png_workspace_bytes.argtypes = [ctypes.POINTER(PngImage), ctypes.c_int]
+    L.md2_png_check.restype = ctypes.c_int
+    L.md2_png_check.argtypes = [ctypes.POINTER(PngImage), ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64]
+    L.md2_png_run.restype = ctypes.c_int
+    L.md2_png_run.argtypes = [_vp, ctypes.c_uint64, ctypes.POINTER(PngImage), _vp, ctypes.c_int, _vp, ctypes.c_size_t,
+                              _vp, ctypes.c_uint64, _vp, _vp]
     L.md2_depth_export16.restype = ctypes.c_int
     L.md2_depth_export16.argtypes = [ctypes.POINTER(Depth16Desc)] + [_vp] * 4
     L.md2_depth_export16_check.restype = ctypes.c_int

@@ -6,7 +6,7 @@ as `python -m monodepth2_amd.convert_dataset --data_path ROOT [--lists FILE ...]
 
 Every `.png` under --data_path (or, with --lists, every frame those split lists name, found as
 `pack_dataset --png` finds them) is decoded by PIL on host threads straight into pinned
-memory, encoded `--batch` at a time by the device encoder (csrc/jpegenc.hip) and written as
+memory (with --device_png: by the device's PNG decoder, csrc/png.hip), encoded `--batch` at a time by the device encoder (csrc/jpegenc.hip) and written as
 NAME.jpg beside it, through a temporary name and os.replace.  Each file is byte-equal to
 `Image.open(png).convert("RGB").save(jpg, quality=Q, subsampling=S)`.  An
 existing .jpg is skipped without --overwrite; --remove_png deletes a PNG only once its .jpg
@@ -23,7 +23,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 from PIL import Image
 
-from . import jpeg_ops
+from . import jpeg_ops, png_ops
 
 
 def png_files(data_path: str) -> List[str]:
@@ -39,10 +39,17 @@ def jpg_path(png: str) -> str:
 
 
 def convert_files(pngs: Sequence[str], quality: int = 92, sampling="4:2:0", overwrite: bool = False,
-                  remove_png: bool = False, device=None, batch: int = 64, threads: int = 8) -> Dict:
+                  remove_png: bool = False, device=None, batch: int = 64, threads: int = 8,
+                  device_png: bool = False) -> Dict:
     """Converts the PNG files `pngs`; returns {"frames", "converted", "skipped", "removed",
-    "bytes_in", "bytes_out"} (bytes of the PNGs read and of the JPEGs written)."""
+    "bytes_in", "bytes_out"} (bytes of the PNGs read and of the JPEGs written).  With
+    device_png the host threads only read and parse: the files png_ops.parse_png takes are
+    decoded on the device into a flat buffer that goes straight into the encoder (the frames
+    never visit the host; "device_decoded" counts them), the others go through PIL as before.
+    The files written are the same bytes either way."""
     stats = {"frames": len(pngs), "converted": 0, "skipped": 0, "removed": 0, "bytes_in": 0, "bytes_out": 0}
+    if device_png:
+        stats["device_decoded"] = 0
     todo = []
     for p in pngs:
         if not overwrite and os.path.exists(jpg_path(p)):
@@ -58,17 +65,39 @@ def convert_files(pngs: Sequence[str], quality: int = 92, sampling="4:2:0", over
         except FileNotFoundError:
             raise FileNotFoundError(f"no such image file {path}") from None
 
+    def parse(path):
+        try:
+            with open(path, "rb") as f:
+                return png_ops.parse_png(f.read())
+        except FileNotFoundError:
+            raise FileNotFoundError(f"no such image file {path}") from None
+
     with ThreadPoolExecutor(max(threads, 1)) as pool:
         for start in range(0, len(todo), batch):
             chunk = todo[start:start + batch]
-            sizes = list(pool.map(size, chunk))
+            parsed = list(pool.map(parse, chunk)) if device_png else [None] * len(chunk)
+            on_device = [i for i, s in enumerate(parsed) if s is not None]
+            by_pil = [i for i, s in enumerate(parsed) if s is None]
+            streams = [None] * len(chunk)
+            if on_device:
+                flat, offsets, shapes = png_ops.decode_png_frames([parsed[i] for i in on_device], device,
+                                                                  names=[chunk[i] for i in on_device])
+                encoded = jpeg_ops.encode_jpeg_batch(flat, quality=quality, sampling=sampling, device=device,
+                                                     check=True, offsets=offsets, sizes=shapes)
+                for i, s in zip(on_device, encoded):
+                    streams[i] = s
+                stats["device_decoded"] += len(on_device)
+            if by_pil:
+                sizes = list(pool.map(size, [chunk[i] for i in by_pil]))
 
-            def fill(i, dest):
-                with Image.open(chunk[i]) as im:
-                    dest[...] = np.asarray(im.convert("RGB"))
+                def fill(k, dest):
+                    with Image.open(chunk[by_pil[k]]) as im:
+                        dest[...] = np.asarray(im.convert("RGB"))
 
-            streams = jpeg_ops.encode_jpeg_batch(sizes, quality=quality, sampling=sampling, device=device,
-                                                 check=True, fill=fill, pool=pool)
+                encoded = jpeg_ops.encode_jpeg_batch(sizes, quality=quality, sampling=sampling, device=device,
+                                                     check=True, fill=fill, pool=pool)
+                for i, s in zip(by_pil, encoded):
+                    streams[i] = s
 
             def write(i):
                 data = jpeg_ops.jpeg_file_bytes(streams[i])     # the stuffing, then the file
@@ -108,6 +137,9 @@ def main(argv: Optional[Sequence[str]] = None):
     ap.add_argument("--overwrite", action="store_true", help="convert also where a .jpg exists")
     ap.add_argument("--batch", type=int, default=64, help="frames encoded per device call")
     ap.add_argument("--threads", type=int, default=8, help="host threads decoding and writing (at most 16)")
+    ap.add_argument("--device_png", action="store_true",
+                    help="decode 8-bit RGB PNG files on the GPU too (HIP kernels, bit-equal to PIL): the frames go "
+                         "from the decoder to the encoder without visiting the host; other files go through PIL")
     args = ap.parse_args(argv)
     jpeg_ops.quality_tables(args.quality)       # refuses a quality outside 1..100 before anything is read
     if args.lists:
@@ -118,7 +150,7 @@ def main(argv: Optional[Sequence[str]] = None):
     else:
         pngs = png_files(args.data_path)
     stats = convert_files(pngs, args.quality, args.sampling, args.overwrite, args.remove_png, batch=args.batch,
-                          threads=min(max(args.threads, 1), 16))
+                          threads=min(max(args.threads, 1), 16), device_png=args.device_png)
     print(json.dumps(stats))
     return stats
 

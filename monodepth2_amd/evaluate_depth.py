@@ -135,7 +135,8 @@ def predict_from_disk(encoder, depth_decoder, opt, lines, feed_hw, device, batch
     dataset = KITTIRAWDataset(opt.data_path, lines, feed_hw[0], feed_hw[1], [0], 1, is_train=False,
                               img_ext=".png" if opt.png else ".jpg")
     loader = BatchLoader(dataset, batch_size, shuffle=False, drop_last=False, num_workers=opt.num_workers,
-                         device=device, device_decode=getattr(opt, "device_decode", False), pack=open_pack(opt))
+                         device=device, device_decode=getattr(opt, "device_decode", False), pack=open_pack(opt),
+                         device_png=getattr(opt, "device_png", False))
     try:
         return _predict_batches(encoder, depth_decoder, (batch[("color", 0, 0)] for batch in loader),
                                 opt.post_process)

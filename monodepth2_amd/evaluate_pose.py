@@ -126,7 +126,8 @@ def predict_from_disk(pose_encoder, pose_decoder, opt, lines, device) -> torch.T
     dataset = KITTIOdomDataset(opt.data_path, lines, opt.height, opt.width, [0, 1], 1, is_train=False,
                                img_ext=".png" if opt.png else ".jpg")
     loader = BatchLoader(dataset, opt.batch_size, shuffle=False, drop_last=False, num_workers=opt.num_workers,
-                         device=device, device_decode=getattr(opt, "device_decode", False), pack=open_pack(opt))
+                         device=device, device_decode=getattr(opt, "device_decode", False), pack=open_pack(opt),
+                         device_png=getattr(opt, "device_png", False))
     try:
         return _predict_pairs(pose_encoder, pose_decoder,
                               ((batch[("color_aug", 0, 0)], batch[("color_aug", 1, 0)]) for batch in loader))

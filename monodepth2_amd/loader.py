@@ -39,6 +39,13 @@ behind the slot's event and are read when the slot is retired: a stream that did
 raises a RuntimeError naming the split line and the file, one or two batches after its own
 or when the epoch ends.
 
+`device_png=True` (implies device_decode) sends 8-bit RGB PNG files the same
+way: a file `jpeg_ops.parse_jpeg` refuses is offered to `png_ops.parse_png`, the deflate
+streams get a region of their own in the staging block behind the JPEG one, `md2_png_run`
+inflates and unfilters them into the ragged buffer, and their status words follow the JPEG
+streams' through the same pinned copy.  Gray, palette, alpha, 16-bit and interlaced files stay
+with PIL (`pil_fallbacks` counts the frames PIL decoded).  Packs hold no PNG streams.
+
 `pack=FramePack(...)` (pack.py) feeds the same device decoder from a packed
 frame file instead of the image files: sizes come from the pack's records and no file is
 opened; the producer thread lays the staging block out (the batch's table bank gathered from
@@ -60,7 +67,7 @@ from typing import Dict, Iterator, List, Optional
 import numpy as np
 import torch
 
-from . import _lib, jpeg_ops
+from . import _lib, jpeg_ops, png_ops
 from .augment import GpuAugmentMixed
 from .datasets import item_seed
 from .pack import KIND_JPEG, frame_key
@@ -93,12 +100,21 @@ class _StagedJpeg:
         self.base, self.jtotal = base, jtotal
         self.pil, self.frames_total, self.names = pil, frames_total, names
         self.index_offsets = None   # a packed batch: where each stream's index lies, for md2_jpeg_run_indexed
+        self.png = None             # device_png: a _StagedPng, the PNG streams' own region of the block
+
+
+class _StagedPng:
+    """The PNG streams of a device-decoded batch: png_ops.describe_png_batch's description and
+    where its region starts in the staging block."""
+
+    def __init__(self, images, n, offset, base, total):
+        self.images, self.n, self.offset, self.base, self.total = images, n, offset, base, total
 
 
 class BatchLoader:
     def __init__(self, dataset, batch_size: int, shuffle: bool = True, seed: int = 0, num_workers: int = 0,
                  rank: int = 0, world_size: int = 1, device=None, with_depth: bool = False, prefetch: int = 2,
-                 drop_last: bool = True, device_decode: bool = False, pack=None):
+                 drop_last: bool = True, device_decode: bool = False, pack=None, device_png: bool = False):
         if not (0 <= rank < world_size):
             raise ValueError(f"rank {rank} outside world size {world_size}")
         if not drop_last and world_size > 1:
@@ -118,7 +134,9 @@ class BatchLoader:
             raise ValueError("with_depth needs a dataset built with load_depth=True whose first split line has "
                              "ground truth (check_depth)")
         self.with_depth = with_depth
-        self.device_decode = bool(device_decode) or pack is not None
+        self.device_png = bool(device_png) and pack is None   # a pack holds no PNG streams
+        self.device_decode = bool(device_decode) or self.device_png or pack is not None
+        self.pil_fallbacks = 0    # device_decode: frames PIL decoded because no device decoder takes their file
         self.pack = pack
         if pack is not None:   # every frame of every split line, before anything is built
             lacking = pack.missing(dataset)
@@ -247,21 +265,32 @@ class BatchLoader:
         def load(n):
             it = items[n % B]
             with open(it.paths[n // B], "rb") as f:
-                s = jpeg_ops.parse_jpeg(f.read())
+                data = f.read()
+            s = jpeg_ops.parse_jpeg(data)
+            if s is None and self.device_png:
+                s = png_ops.parse_png(data)
             if s is not None and (s.height, s.width) == it.size:
                 return s
             return self.dataset.decode(it.images[n // B])
 
         got = self._map(load, range(F * B))
         on_device = [n for n in range(F * B) if isinstance(got[n], jpeg_ops.JpegStream)]
+        as_png = [n for n in range(F * B) if isinstance(got[n], png_ops.PngStream)]
         streams = [got[n] for n in on_device]
         images, quant, huff, base, pos = None, [], [], 0, 0
         if streams:
             images, quant, huff, base, pos = jpeg_ops.describe_batch(streams, [offsets[n] for n in on_device])
             jpeg_ops.check_described(images, len(streams), len(quant), len(huff), pos - base, frames_total)
-        jtotal, pil = pos, []
+        jtotal, pil, png = pos, [], None
+        if as_png:   # their own region behind the JPEG one
+            pos = (pos + ALIGN - 1) // ALIGN * ALIGN
+            pstreams = [got[n] for n in as_png]
+            pimages, pbase, ptotal = png_ops.describe_png_batch(pstreams, [offsets[n] for n in as_png])
+            png_ops.check_png_described(pimages, len(pstreams), ptotal - pbase, frames_total)
+            png = _StagedPng(pimages, len(pstreams), pos, pbase, ptotal)
+            pos += ptotal
         for n in range(F * B):
-            if not isinstance(got[n], jpeg_ops.JpegStream):
+            if not isinstance(got[n], (jpeg_ops.JpegStream, png_ops.PngStream)):
                 pos = (pos + ALIGN - 1) // ALIGN * ALIGN
                 pil.append((n, pos, got[n].size))
                 pos += got[n].size
@@ -273,11 +302,16 @@ class BatchLoader:
             host = buf.numpy()
         if streams:
             jpeg_ops.fill_staging(host, streams, images, quant, huff, base)
+        if png is not None:
+            png_ops.fill_png_staging(host[png.offset:png.offset + png.total], pstreams, png.images, png.base)
         for n, o, size in pil:
             host[o:o + size] = got[n].reshape(-1)
-        names = [(items[n % B].index, items[n % B].line, items[n % B].paths[n // B]) for n in on_device]
+        self.pil_fallbacks += len(pil)
+        names = [(items[n % B].index, items[n % B].line, items[n % B].paths[n // B], "jpeg") for n in on_device]
+        names += [(items[n % B].index, items[n % B].line, items[n % B].paths[n // B], "png") for n in as_png]
         st = _Staged(slot, total, offsets, items, spill)
         st.jpeg = _StagedJpeg(images, len(streams), len(quant), len(huff), base, jtotal, pil, frames_total, names)
+        st.jpeg.png = png
         return st
 
     def _stage_packed(self, items, offsets, frames_total: int, slot: int) -> _Staged:
@@ -334,7 +368,7 @@ class BatchLoader:
             host[:nq] = pack.quant[list(quant)].reshape(-1)
             host[nq:nq + nh] = pack.huff[list(huff)].reshape(-1)
         self._map(lambda rd: pack.read_into(rd[0], host[rd[1]:rd[1] + rd[2]]), reads)
-        names = [(items[n % B].index, items[n % B].line, items[n % B].paths[n // B]) for n in on_device]
+        names = [(items[n % B].index, items[n % B].line, items[n % B].paths[n // B], "jpeg") for n in on_device]
         st = _Staged(slot, total, offsets, items, spill)
         st.jpeg = _StagedJpeg(images, nj, len(quant), len(huff), base, jtotal, pil, frames_total, names)
         st.jpeg.index_offsets = index_offsets
@@ -374,6 +408,13 @@ class BatchLoader:
         before the slot's event is recorded)."""
         j = st.jpeg
         frames = torch.empty(j.frames_total, dtype=torch.uint8, device=self.device)
+        words = j.n + (j.png.n if j.png is not None else 0)
+        if words:
+            host = self._status[st.slot]
+            if host is None or host.numel() < words:
+                host = self._status[st.slot] = torch.empty(max(words, len(self.frame_ids) * self.batch_size),
+                                                           dtype=torch.int32, pin_memory=True)
+            self._status_of[st.slot] = j.names   # the JPEG streams' words, then the PNG streams'
         if j.n:
             if j.index_offsets is not None:
                 status = jpeg_ops.run_staged_indexed(up, j.images, j.index_offsets, j.n, j.num_quant, j.num_huff,
@@ -381,12 +422,12 @@ class BatchLoader:
             else:
                 status = jpeg_ops.run_staged(up, j.images, j.n, j.num_quant, j.num_huff, j.base, j.jtotal, frames,
                                              self.device)
-            host = self._status[st.slot]
-            if host is None or host.numel() < j.n:
-                host = self._status[st.slot] = torch.empty(max(j.n, len(self.frame_ids) * self.batch_size),
-                                                           dtype=torch.int32, pin_memory=True)
             host[:j.n].copy_(status, non_blocking=True)
-            self._status_of[st.slot] = j.names
+        if j.png is not None:
+            p = j.png
+            status = png_ops.run_png_staged(up[p.offset:p.offset + p.total], p.images, p.n, p.base, p.total, frames,
+                                            self.device)
+            host[j.n:words].copy_(status, non_blocking=True)
         for n, o, size in j.pil:
             frames[st.offsets[n]:st.offsets[n] + size].copy_(up[o:o + size], non_blocking=True)
         return frames
@@ -399,9 +440,10 @@ class BatchLoader:
         words = self._status[slot][:len(names)].tolist()
         bad = [(w, name) for w, name in zip(words, names) if w]
         if bad:
-            w, (index, line, path) = bad[0]
-            why = ("the pack's synchronisation index does not fit the stream, or the stream does not hold the image's "
-                   "blocks" if w & _lib.JPEG_ST_INDEX
+            w, (index, line, path, kind) = bad[0]
+            why = (png_ops.status_text(w) if kind == "png"
+                   else "the pack's synchronisation index does not fit the stream, or the stream does not hold the "
+                   "image's blocks" if w & _lib.JPEG_ST_INDEX
                    else "the entropy-coded data does not hold the image's blocks")
             raise RuntimeError(f"split line {index} ({line!r}): {path} did not decode on the device (status {w}: "
                                f"{why}); {len(bad)} bad file(s) in its batch")

@@ -25,6 +25,9 @@ _FLAGS = [
     ("--png", dict(action="store_true", help="train from png instead of jpg")),
     ("--device_decode", dict(action="store_true", help="decode baseline JPEG frames on the GPU (HIP kernels, "
                                                         "bit-equal to PIL); other files still go through PIL")),
+    ("--device_png", dict(action="store_true", help="build: decode 8-bit RGB PNG frames on the GPU too (inflate "
+                                                     "and unfilter in HIP kernels, bit-equal to PIL); implies "
+                                                     "--device_decode; other files still go through PIL")),
     ("--pack", dict(type=str, help="build: feed the frames from this packed frame file (python -m "
                                    "monodepth2_amd.pack_dataset) instead of the image files under --data_path; "
                                    "implies --device_decode; ground-truth depth is still read from --data_path")),

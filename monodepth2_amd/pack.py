@@ -48,7 +48,7 @@ from typing import Dict, Iterable, Iterator, List, Optional, Sequence, Tuple
 import numpy as np
 from PIL import Image
 
-from . import jpeg_ops
+from . import jpeg_ops, png_ops
 from ._lib import JPEG_HUFF_BYTES, JPEG_QUANT_BYTES
 
 MAGIC = b"MD2PACK\0"
@@ -343,12 +343,18 @@ def frame_paths(data_path: str, line_lists: Sequence[Sequence[str]], dataset: st
 
 
 def records_from_files(paths: Dict[str, str], device=None, batch: int = 64, threads: int = 8,
-                       transcode: Optional[Tuple[int, object]] = None) -> Iterator[PackRecord]:
+                       transcode: Optional[Tuple[int, object]] = None,
+                       device_png: bool = False) -> Iterator[PackRecord]:
     """The records of the files {key: path}, in key order: read and parsed by `threads` host
     threads, the supported JPEG files indexed on the device `batch` at a time, every other
     file decoded with PIL into a RAW record.  transcode=(quality, sampling): such a file is
     encoded on the device after PIL decoded it, indexed with the rest of its batch and
-    becomes a JPEG record under its own key, marked as transcoded."""
+    becomes a JPEG record under its own key, marked as transcoded.  With device_png as well,
+    the PNG files png_ops.parse_png takes are not decoded by PIL: the device decodes them into
+    a flat buffer that goes straight into the encoder (the same records, byte for byte).  RAW
+    records keep the PIL route: their frames have to be on the host anyway."""
+    on_device_png = bool(device_png) and transcode is not None
+
     def load(key):
         path = paths[key]
         try:
@@ -357,6 +363,8 @@ def records_from_files(paths: Dict[str, str], device=None, batch: int = 64, thre
         except FileNotFoundError:
             raise FileNotFoundError(f"no such image file {path} (frame {key})") from None
         s = jpeg_ops.parse_jpeg(data)
+        if s is None and on_device_png:
+            s = png_ops.parse_png(data)
         if s is not None:
             return s
         with Image.open(path) as im:
@@ -369,6 +377,15 @@ def records_from_files(paths: Dict[str, str], device=None, batch: int = 64, thre
             got = list(pool.map(load, chunk))
             encoded = {}
             if transcode is not None:
+                pngs = [n for n, g in enumerate(got) if isinstance(g, png_ops.PngStream)]
+                if pngs:
+                    flat, offsets, sizes = png_ops.decode_png_frames([got[n] for n in pngs], device,
+                                                                     names=[paths[chunk[n]] for n in pngs])
+                    streams = jpeg_ops.encode_jpeg_batch(flat, quality=transcode[0], sampling=transcode[1],
+                                                         device=device, check=True, offsets=offsets, sizes=sizes)
+                    for n, s in zip(pngs, streams):
+                        got[n] = s
+                        encoded[n] = int(transcode[0])
                 lossless = [n for n, g in enumerate(got) if not isinstance(g, jpeg_ops.JpegStream)]
                 streams = jpeg_ops.encode_jpeg_batch([got[n] for n in lossless], quality=transcode[0],
                                                      sampling=transcode[1], device=device, check=True)
@@ -386,11 +403,13 @@ def records_from_files(paths: Dict[str, str], device=None, batch: int = 64, thre
 
 def build_pack(out: str, data_path: str, line_lists: Sequence[Sequence[str]], dataset: str = "kitti",
                png: bool = False, frame_ids: Sequence = (0, -1, 1), use_stereo: bool = False, device=None,
-               batch: int = 64, threads: int = 8, transcode: Optional[Tuple[int, object]] = None) -> Dict:
+               batch: int = 64, threads: int = 8, transcode: Optional[Tuple[int, object]] = None,
+               device_png: bool = False) -> Dict:
     """Parse, index on the device, write: the frames the split lines of `line_lists` name
     under `data_path`, into the pack `out`.  Files are read by `threads` host threads and
     indexed `batch` at a time.  transcode=(quality, sampling): files the device decoder does
-    not take are encoded as JPEG on the device instead of stored decoded (records_from_files).
+    not take are encoded as JPEG on the device instead of stored decoded (records_from_files);
+    device_png: the PNG files among them are decoded on the device too.
     Returns {"frames", "jpeg", "raw", "transcoded", "pack_bytes", "file_bytes"} (file_bytes:
     the size of the image files read; transcoded frames count as jpeg too)."""
     paths = frame_paths(data_path, line_lists, dataset, png, frame_ids, use_stereo)
@@ -400,7 +419,7 @@ def build_pack(out: str, data_path: str, line_lists: Sequence[Sequence[str]], da
         jpeg_ops.quality_tables(transcode[0])
 
     def counted():
-        for rec in records_from_files(paths, device, batch, threads, transcode):
+        for rec in records_from_files(paths, device, batch, threads, transcode, device_png):
             stats["jpeg" if rec.stream is not None else "raw"] += 1
             stats["transcoded"] += 1 if rec.transcoded else 0
             stats["file_bytes"] += os.path.getsize(paths[rec.name])

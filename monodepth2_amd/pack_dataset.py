@@ -7,7 +7,8 @@ would (--dataset, --png, --frame_ids and --use_stereo as there), and writes the 
 synchronisation indexes are computed by the device decoder's own kernel.  With --png
 --transcode [--quality 92] [--sampling 420] the PNG frames are encoded as JPEG on the device
 (csrc/jpegenc.hip) instead of stored decoded: the pack `convert_dataset` followed by
-`pack_dataset` would give, without writing the .jpg files.
+`pack_dataset` would give, without writing the .jpg files; with --device_png on top the PNG
+files are decoded on the device as well (csrc/png.hip), the same pack.
 """
 from __future__ import annotations
 
@@ -33,13 +34,17 @@ def main(argv: Optional[Sequence[str]] = None):
                          "storing them decoded: a much smaller pack, lossy like convert_dataset")
     ap.add_argument("--quality", type=int, default=92, help="of --transcode")
     ap.add_argument("--sampling", default="420", choices=["444", "422", "420"], help="of --transcode")
+    ap.add_argument("--device_png", action="store_true",
+                    help="with --png --transcode: decode the 8-bit RGB PNG files on the GPU too (HIP kernels, "
+                         "bit-equal to PIL), so the frames go from decoder to encoder without visiting the host")
     ap.add_argument("--batch", type=int, default=64, help="files indexed per device call")
     ap.add_argument("--threads", type=int, default=8, help="host threads reading and parsing files (at most 16)")
     args = ap.parse_args(argv)
     stats = build_pack(args.out, args.data_path, [readlines(p) for p in args.lists], dataset=args.dataset,
                        png=args.png, frame_ids=args.frame_ids, use_stereo=args.use_stereo, batch=args.batch,
                        threads=min(max(args.threads, 1), 16),
-                       transcode=(args.quality, args.sampling) if args.transcode else None)
+                       transcode=(args.quality, args.sampling) if args.transcode else None,
+                       device_png=args.device_png)
     stats["out"] = args.out
     print(json.dumps(stats))
     return stats

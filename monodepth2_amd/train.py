@@ -50,7 +50,8 @@ def build_loaders(opt, trainer: Trainer):
     frame_ids = list(trainer.opt.frame_ids)   # with "s" appended under --use_stereo
     common = dict(batch_size=opt.batch_size, shuffle=True, num_workers=opt.num_workers, rank=trainer.rank,
                   world_size=trainer.world_size, device=trainer.device,
-                  device_decode=getattr(opt, "device_decode", False), pack=open_pack(opt))
+                  device_decode=getattr(opt, "device_decode", False), pack=open_pack(opt),
+                  device_png=getattr(opt, "device_png", False))
     train_set = cls(opt.data_path, train_lines, opt.height, opt.width, frame_ids, num_scales, is_train=True,
                     img_ext=img_ext, seed=opt.seed)
     # depth_gt feeds the validation monitor only (Trainer.val_step)
