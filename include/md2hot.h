@@ -1212,6 +1212,87 @@ int md2_png_run(const uint8_t* streams, uint64_t streams_bytes, const md2_png_im
                 uint64_t out_bytes, uint32_t* status, void* stream);
 
 /*
+ * The indexed PNG decoder (csrc/png.hip): md2_png_run decodes a stream serially, so a call
+ * lasts as long as one stream.  Where a stream's symbols start is a property of the file: it
+ * is found once (md2_png_index, when a frame pack is built) and stored beside the stream;
+ * md2_png_run_indexed then inflates all segments of all streams at the same time.  New
+ * symbols under ABI 24, no version bump.
+ *
+ * The index of a stream cuts its output, the height * (1 + 3 width) scanline bytes, into
+ * consecutive segments for one value of segment_bytes, S: a power of two in 1024..32768.
+ * Walking the stream as md2_png_run does, a boundary candidate is a block header, the start
+ * of a literal/length symbol (the end-of-block symbol included) in a fixed or dynamic block,
+ * and every byte of a stored block.  Segment 0 starts at bit 0 and output 0; a new segment
+ * starts at the first candidate at which the current one has produced at least S bytes, so
+ * every segment but the last holds S..S + 257 bytes and there are at most raw_bytes / S + 1.
+ * No segment starts at the image's end.  The layout (little-endian, fixed per geometry and S):
+ *
+ *   bytes 0..15   u32 count (segments; 0: the stream did not inflate, nothing decodes from
+ *                 this index), u32 segment_bytes, 8 zero bytes
+ *   then          raw_bytes / S + 1 entries of 24 bytes, the first `count` in use, the rest 0:
+ *                   u64 header_bit   bit offset of the 3-bit header of the block the segment starts in
+ *                   u64 symbol_bit   bit offset of the segment's first symbol (a stored block:
+ *                                    of its first byte; at a block's start: header_bit)
+ *                   u32 out_pos      output position of the segment's first byte
+ *                   u32 0
+ *   zeros up to a multiple of 16: md2_png_index_bytes(height, width, segment_bytes) in all
+ *   (0 and md2_last_error for a geometry or an S the decoder refuses).
+ *
+ * md2_png_index: streams, images and dev_images as for md2_png_run (out_offset is not used);
+ * makes the index alone with md2_png_run's serial walk (one wave per stream, no byte of the
+ * frame is produced) and writes image i's index at index + index_offsets[i] (`index`: DEVICE
+ * bytes, 16-byte aligned, index_bytes long; index_offsets: HOST array of n multiples of 16,
+ * dev_index_offsets a DEVICE copy of it, 8-byte aligned, as dev_images is of images).
+ * status: the bits of md2_png_run's inflate stage (BLOCK, CODE, END, DIST); a stream with a
+ * bit set gets count 0.  FILTER and ADLER are not looked at.
+ *
+ * md2_png_run_indexed: md2_png_run's contract, with image i's index read from streams +
+ * index_offsets[i] (where a pack record's bytes put it: behind the stream) and a workspace of
+ * md2_png_indexed_workspace_bytes (the scanlines as for md2_png_run, a 16-bit symbol per
+ * scanline byte, a status word per segment; 16-byte aligned, no initialisation needed).
+ * Three launches on `stream`, ordered by their boundaries alone (no workgroup waits for
+ * another's memory), no allocation, no host synchronisation, hipGraph-capturable:
+ *   segments  one wave per (image, segment), the grid as wide as the batch's largest
+ *             capacity: re-reads the block header at header_bit, rebuilds its tables, seeks to
+ *             symbol_bit and decodes up to the next entry's out_pos (the last: the image's
+ *             end) into 16-bit symbols held in LDS (S + 257 positions): b for a known byte,
+ *             0x8000 | k for "the byte k + 1 before this segment's start" (k in 0..32767: every
+ *             legal distance); a copy from inside the segment copies symbols
+ *   resolve   one workgroup per image: ORs the segments' status words into the image's;
+ *             if that is 0, turns symbols into bytes segment after segment behind its own
+ *             barrier, so a reference through several segments finds a final byte
+ *   unfilter  md2_png_run's second launch, unchanged
+ * The index is not trusted.  Every wave checks its entry (bits inside the stream, header_bit
+ * <= symbol_bit, out_pos ascending, inside the image and at most S + 257 before the next,
+ * entry 0 at bit 0 and output 0, count within capacity, the stored S the call's) and its exit against
+ * the next entry (exactly on out_pos, the same symbol_bit, in the same block), and that it
+ * met no candidate S or more bytes into its range (a boundary the index lacks); a mismatch
+ * sets MD2_PNG_ST_INDEX in the image's status word, a distance reaching before byte 0
+ * MD2_PNG_ST_DIST.  Whatever the index says, a wave writes only the symbols of its own output
+ * range and its own status word, and reads stay inside streams.  With an inflate-stage bit
+ * or INDEX set the frame is not written, and the other images are unaffected.  With its true
+ * index a stream gives md2_png_run's bytes and status exactly.
+ *
+ * Refused (MD2_ERR_ARG) before anything is launched: what md2_png_run refuses, NULL
+ * index_offsets or dev_index_offsets, an index offset that is no multiple of 16, an index that
+ * leaves streams_bytes, a segment_bytes that is no power of two in 1024..32768.
+ * md2_png_check_indexed runs the checks that need no device pointer alone (host only).
+ */
+#define MD2_PNG_ST_INDEX  (1u << 6)  /* the index does not fit the stream (md2_png_run_indexed) */
+
+size_t md2_png_index_bytes(int height, int width, int segment_bytes);
+size_t md2_png_indexed_workspace_bytes(const md2_png_image* images, int n, int segment_bytes);
+int md2_png_index(const uint8_t* streams, uint64_t streams_bytes, const md2_png_image* images,
+                  const md2_png_image* dev_images, int n, int segment_bytes, uint8_t* index, uint64_t index_bytes,
+                  const uint64_t* index_offsets, const uint64_t* dev_index_offsets, uint32_t* status, void* stream);
+int md2_png_check_indexed(const md2_png_image* images, const uint64_t* index_offsets, int n, int segment_bytes,
+                          uint64_t streams_bytes, uint64_t out_bytes);
+int md2_png_run_indexed(const uint8_t* streams, uint64_t streams_bytes, const md2_png_image* images,
+                        const md2_png_image* dev_images, const uint64_t* index_offsets,
+                        const uint64_t* dev_index_offsets, int n, int segment_bytes, uint8_t* workspace,
+                        size_t workspace_bytes, uint8_t* out, uint64_t out_bytes, uint32_t* status, void* stream);
+
+/*
  * The training log's pictures (csrc/md2hot.hip): what the reference's Trainer.log writes at
  * a log step (trainer.py:540-572, with normalize_image, utils.py:22-28) for the first
  * `items` images of the batch, as one uint8 contact sheet (items, sheet_h, sheet_w, 3) filled

@@ -83,6 +83,8 @@ EXPORTS = ["md2_abi_version", "md2_last_error", "md2_workspace_bytes", "md2_sele
            "md2_jpeg_index_bytes", "md2_jpeg_index", "md2_jpeg_check_indexed", "md2_jpeg_run_indexed",
            "md2_jpeg_encode_bound", "md2_jpeg_encode_workspace_bytes", "md2_jpeg_encode_check", "md2_jpeg_encode",
            "md2_png_workspace_bytes", "md2_png_check", "md2_png_run",
+           "md2_png_index_bytes", "md2_png_indexed_workspace_bytes", "md2_png_index", "md2_png_check_indexed",
+           "md2_png_run_indexed",
            "md2_log_panel_tile_blocks", "md2_log_panel_check", "md2_log_panel_workspace_bytes", "md2_log_panel",
            "md2_depth_points", "md2_depth_points_workspace_bytes"]
 
@@ -267,6 +269,8 @@ class JpegEncImage(ctypes.Structure):
 
 # md2_png_run (csrc/png.hip): new symbols under ABI 24, no version bump
 PNG_ST_BLOCK, PNG_ST_CODE, PNG_ST_END, PNG_ST_DIST, PNG_ST_FILTER, PNG_ST_ADLER = 1, 2, 4, 8, 16, 32
+PNG_ST_INDEX = 64   # md2_png_run_indexed: the index does not fit the stream
+PNG_INDEX_HEADER_BYTES, PNG_INDEX_ENTRY_BYTES = 16, 24   # the index layout (include/md2hot.h)
 
 
 class PngImage(ctypes.Structure):
@@ -358,6 +362,20 @@ def _declare(L):
     L.md2_png_run.restype = ctypes.c_int
     L.md2_png_run.argtypes = [_vp, ctypes.c_uint64, ctypes.POINTER(PngImage), _vp, ctypes.c_int, _vp, ctypes.c_size_t,
                               _vp, ctypes.c_uint64, _vp, _vp]
+    _u64p = ctypes.POINTER(ctypes.c_uint64)
+    L.md2_png_index_bytes.restype = ctypes.c_size_t
+    L.md2_png_index_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    L.md2_png_indexed_workspace_bytes.restype = ctypes.c_size_t
+    L.md2_png_indexed_workspace_bytes.argtypes = [ctypes.POINTER(PngImage), ctypes.c_int, ctypes.c_int]
+    L.md2_png_index.restype = ctypes.c_int
+    L.md2_png_index.argtypes = [_vp, ctypes.c_uint64, ctypes.POINTER(PngImage), _vp, ctypes.c_int, ctypes.c_int, _vp,
+                                ctypes.c_uint64, _u64p, _vp, _vp, _vp]
+    L.md2_png_check_indexed.restype = ctypes.c_int
+    L.md2_png_check_indexed.argtypes = [ctypes.POINTER(PngImage), _u64p, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,
+                                        ctypes.c_uint64]
+    L.md2_png_run_indexed.restype = ctypes.c_int
+    L.md2_png_run_indexed.argtypes = [_vp, ctypes.c_uint64, ctypes.POINTER(PngImage), _vp, _u64p, _vp, ctypes.c_int,
+                                      ctypes.c_int, _vp, ctypes.c_size_t, _vp, ctypes.c_uint64, _vp, _vp]
     L.md2_depth_export16.restype = ctypes.c_int
     L.md2_depth_export16.argtypes = [ctypes.POINTER(Depth16Desc)] + [_vp] * 4
     L.md2_depth_export16_check.restype = ctypes.c_int

@@ -90,7 +90,7 @@ struct Reader {
     int lane;
 
     // Bytes past the stream's end read as zero; the decoder notices through overrun().
-    __device__ uint4 load(uint32_t chunk) const {
+    __device__ __forceinline__ uint4 load(uint32_t chunk) const {
         const uint64_t off = (uint64_t)chunk * kChunkBytes + 16u * lane;
         if (off + 16 <= nbytes) return *reinterpret_cast<const uint4*>(src + off);
         uint32_t w0 = 0, w1 = 0, w2 = 0, w3 = 0;
@@ -104,9 +104,11 @@ struct Reader {
         }
         return make_uint4(w0, w1, w2, w3);
     }
-    __device__ void store(uint32_t half, uint4 v) { reinterpret_cast<uint4*>(in)[(half & 1) * kWave + lane] = v; }
+    __device__ __forceinline__ void store(uint32_t half, uint4 v) {
+        reinterpret_cast<uint4*>(in)[(half & 1) * kWave + lane] = v;
+    }
 
-    __device__ void refill() {
+    __device__ __forceinline__ void refill() {
         if (bc <= 32) {
             const uint32_t w = uniform(in[inword & (kInWords - 1)]);
             bb |= (uint64_t)w << bc;
@@ -134,7 +136,7 @@ struct Reader {
     __device__ uint32_t no_code() const {
         return consumed() + 15 > (uint64_t)nbytes * 8 ? MD2_PNG_ST_END : MD2_PNG_ST_CODE;
     }
-    __device__ void seek(uint32_t byte) {
+    __device__ __forceinline__ void seek(uint32_t byte) {
         const uint32_t c = byte / kChunkBytes;
         wave_sync();
         store(c, load(c));
@@ -146,6 +148,10 @@ struct Reader {
         bc = 0;
         refill();
         drop(8 * (byte & 3));
+    }
+    __device__ __forceinline__ void seek_bit(uint64_t bit) {   // bit <= 8 * nbytes
+        seek((uint32_t)(bit >> 3));
+        drop((uint32_t)bit & 7);               // a seek leaves at least 8 bits
     }
 };
 
@@ -201,7 +207,7 @@ __device__ int build(Huff& h, const uint8_t* lens, int n, bool code_lengths, uin
 }
 
 // One symbol, or -1 for a bit pattern that is no code.  Needs 15 bits in the buffer.
-__device__ int decode(const Huff& h, Reader& br) {
+__device__ __forceinline__ int decode(const Huff& h, Reader& br) {
     const uint32_t e = uniform(h.primary[(uint32_t)br.bb & (kPrimary - 1)]);
     if (e) {
         br.drop(e & 15);
@@ -224,31 +230,88 @@ __device__ int decode(const Huff& h, Reader& br) {
     return -1;
 }
 
-__global__ __launch_bounds__(kWave) void png_inflate_kernel(const uint8_t* __restrict__ streams,
-                                                            const md2_png_image* __restrict__ images,
-                                                            uint8_t* __restrict__ workspace,
-                                                            uint32_t* __restrict__ status) {
-    __shared__ __attribute__((aligned(16))) uint8_t ring[kRing];
-    __shared__ __attribute__((aligned(16))) uint32_t in[kInWords];
-    __shared__ Huff lit, dst;
-    __shared__ uint8_t lens[320];
-    __shared__ uint8_t cl_lens[19];
-    __shared__ uint16_t codes[320];
-    __shared__ uint16_t work[32];
+// What the walk of a stream's blocks needs in LDS besides its window.
+struct Scratch {
+    Huff lit, dst;
+    uint8_t lens[320];
+    uint8_t cl_lens[19];
+    uint16_t codes[320];
+    uint16_t work[32];
+};
 
-    const int img = blockIdx.x, lane = threadIdx.x;
-    const md2_png_image im = images[img];
-    const uint32_t total = (uint32_t)raw_bytes(im.height, im.width);
-    uint8_t* ws = workspace + workspace_offset(images, img, lane);
+// One entry of a stream's index (md2hot.h): where a segment of the output starts.
+struct IndexEntry {
+    unsigned long long header_bit;   // the 3-bit header of the block the segment starts in
+    unsigned long long symbol_bit;   // the segment's first symbol (a stored block: its first byte)
+    uint32_t out_pos;                // the output position the segment starts at
+    uint32_t zero;
+};
+static_assert(sizeof(IndexEntry) == 24, "the index layout of md2hot.h");
+constexpr uint32_t kIndexHeader = 16;   // u32 count, u32 segment_bytes, 8 zero bytes
+constexpr uint32_t kMaxSymbol = 258;    // the most one symbol adds to the output
 
-    Reader br;
-    br.src = streams + im.stream_offset;
-    br.nbytes = im.stream_bytes;
-    br.in = in;
-    br.lane = lane;
-    br.seek(0);
+// The three uses of the one walk: kRun inflates into the 32 KiB byte ring and the workspace
+// (md2_png_run); kIndex follows the same symbols, writes no byte and records where segments
+// start; kSegment enters at an index entry and decodes one segment into 16-bit symbols.
+enum Mode { kRun, kIndex, kSegment };
 
-    uint32_t pos = 0, flushed = 0, st = 0;
+// kIndex: the entries found so far.  Every lane holds the same state; lane 0 writes.
+struct Indexer {
+    IndexEntry* entries;
+    uint32_t cap, count, seg_start, segment_bytes;
+    // a boundary candidate at output position pos: a new segment starts here if the current one is full
+    __device__ void candidate(uint64_t header_bit, uint64_t symbol_bit, uint32_t pos, int lane) {
+        if (pos - seg_start < segment_bytes) return;
+        if (count < cap && lane == 0) {
+            IndexEntry e;
+            e.header_bit = header_bit;
+            e.symbol_bit = symbol_bit;
+            e.out_pos = pos;
+            e.zero = 0;
+            entries[count] = e;
+        }
+        ++count;
+        seg_start = pos;
+    }
+};
+
+// kSegment: the entry the wave starts from and where it stopped.
+struct Segment {
+    uint64_t header_bit, symbol_bit;
+    uint32_t start, limit;   // the segment's output range
+    uint32_t segment_bytes;  // S: a candidate at or past start + S inside the range is a boundary the index lacks
+    bool last;               // the image's last segment: limit is the image's end
+    uint64_t exit_header, exit_symbol;   // the candidate the wave stopped at (not for the last segment)
+};
+
+// The walk of one stream's blocks by one wave.  Returns the status bits of the inflate stage;
+// `pos` is where the output stands afterwards.  window: kRun the byte ring (kRing bytes),
+// kSegment the segment's symbols (uint16, position p at p - sg.start), kIndex unused.
+template <int M>
+__device__ __forceinline__ uint32_t inflate_walk(Reader& br, Scratch& sc, const uint32_t total, const int lane,
+                                                 void* window, uint8_t* ws, Indexer& ix, Segment& sg, uint32_t& pos) {
+    Huff& lit = sc.lit;
+    Huff& dst = sc.dst;
+    uint8_t* const lens = sc.lens;
+    uint8_t* const cl_lens = sc.cl_lens;
+    uint16_t* const codes = sc.codes;
+    uint16_t* const work = sc.work;
+    uint8_t* const ring = static_cast<uint8_t*>(window);
+    uint16_t* const seg = static_cast<uint16_t*>(window);
+
+    uint32_t flushed = 0, st = 0;
+    uint32_t limit = total;      // where the output of this walk ends
+    bool entering = false;       // kSegment: the first symbol is not the block's first
+    bool stopped = false;        // kSegment: the walk reached its limit at a candidate
+    pos = 0;
+    if constexpr (M == kSegment) {
+        pos = sg.start;
+        limit = sg.limit;
+        entering = sg.symbol_bit != sg.header_bit;
+        br.seek_bit(sg.header_bit);
+    } else {
+        br.seek(0);
+    }
 
     // the ring's bytes [flushed, upto) to the workspace; upto is a multiple of 16, at most align16(total)
     auto flush = [&](uint32_t upto) {
@@ -260,6 +323,19 @@ __global__ __launch_bounds__(kWave) void png_inflate_kernel(const uint8_t* __res
 
     while (true) {
         br.refill();
+        [[maybe_unused]] const uint64_t header = br.consumed();   // a block header is a boundary candidate
+        if constexpr (M == kIndex) ix.candidate(header, header, pos, lane);
+        if constexpr (M == kSegment) {
+            if (pos >= limit) {   // only a segment that is not the last comes here
+                sg.exit_header = sg.exit_symbol = header;
+                stopped = true;
+                break;
+            }
+            if (pos - sg.start >= sg.segment_bytes) {   // a new segment starts at the FIRST such candidate
+                st = MD2_PNG_ST_INDEX;
+                break;
+            }
+        }
         const uint32_t last = br.bits(1), type = br.bits(2);
         if (type == 3) {
             st = MD2_PNG_ST_BLOCK;
@@ -268,7 +344,7 @@ __global__ __launch_bounds__(kWave) void png_inflate_kernel(const uint8_t* __res
         if (type == 0) {
             br.drop(br.bc & 7);
             br.refill();
-            const uint32_t len = br.bits(16);
+            uint32_t len = br.bits(16);
             br.refill();
             const uint32_t nlen = br.bits(16);
             if (br.overrun()) break;
@@ -276,22 +352,71 @@ __global__ __launch_bounds__(kWave) void png_inflate_kernel(const uint8_t* __res
                 st = MD2_PNG_ST_BLOCK;
                 break;
             }
+            uint32_t byte = (uint32_t)(br.consumed() >> 3);
+            if constexpr (M == kSegment) {
+                if (entering) {   // the entry names a byte inside this block
+                    entering = false;
+                    const uint32_t first = (uint32_t)(sg.symbol_bit >> 3);   // symbol_bit <= 8 * nbytes
+                    if ((sg.symbol_bit & 7) || first < byte || first - byte >= len) {
+                        st = MD2_PNG_ST_INDEX;
+                        break;
+                    }
+                    len -= first - byte;
+                    byte = first;
+                }
+            }
             if (len) {
-                uint32_t byte = (uint32_t)(br.consumed() >> 3);
                 const uint32_t have = br.nbytes - byte;            // no overrun: byte <= nbytes
                 uint32_t n = len < have ? len : have;
-                if (n > total - pos) n = total - pos;
+                if (n > limit - pos) n = limit - pos;
                 const uint32_t end = byte + len;
-                while (n) {
-                    const uint32_t piece = n < kFlush ? n : kFlush;
-                    wave_sync();
-                    for (uint32_t i = lane; i < piece; i += kWave) ring[(pos + i) & kRingMask] = br.src[byte + i];
-                    pos += piece;
-                    byte += piece;
-                    n -= piece;
-                    if (pos - flushed >= kFlush) flush(pos & ~15u);
+                if constexpr (M == kSegment) {   // every byte is a candidate: the last one copied too
+                    if (n && pos + n - 1 - sg.start >= sg.segment_bytes) {
+                        st = MD2_PNG_ST_INDEX;
+                        break;
+                    }
                 }
-                if (pos >= total) break;
+                if constexpr (M == kIndex) {   // every byte of the block is a candidate
+                    uint32_t done = 0;
+                    while (done < n) {
+                        const uint32_t made = pos + done - ix.seg_start;
+                        if (made >= ix.segment_bytes) {
+                            ix.candidate(header, 8ull * (byte + done), pos + done, lane);
+                            continue;
+                        }
+                        const uint32_t step = ix.segment_bytes - made;
+                        done += step < n - done ? step : n - done;
+                    }
+                    pos += n;
+                    byte += n;
+                } else {
+                    while (n) {
+                        const uint32_t piece = n < kFlush ? n : kFlush;
+                        wave_sync();
+                        if constexpr (M == kRun) {
+                            for (uint32_t i = lane; i < piece; i += kWave)
+                                ring[(pos + i) & kRingMask] = br.src[byte + i];
+                        } else {
+                            for (uint32_t i = lane; i < piece; i += kWave) seg[pos - sg.start + i] = br.src[byte + i];
+                        }
+                        pos += piece;
+                        byte += piece;
+                        n -= piece;
+                        if constexpr (M == kRun)
+                            if (pos - flushed >= kFlush) flush(pos & ~15u);
+                    }
+                }
+                if constexpr (M == kSegment) {
+                    if (pos >= limit && !sg.last && byte < end) {   // the next byte of the block is the candidate
+                        sg.exit_header = header;
+                        sg.exit_symbol = 8ull * byte;
+                        stopped = true;
+                        break;
+                    }
+                    if (pos >= limit && sg.last) break;
+                } else {
+                    if (pos >= total) break;
+                }
                 if (len > have) {
                     st = MD2_PNG_ST_END;
                     break;
@@ -365,15 +490,36 @@ __global__ __launch_bounds__(kWave) void png_inflate_kernel(const uint8_t* __res
                     break;
                 }
             }
+            if constexpr (M == kSegment) {
+                if (entering) {   // the entry names a symbol behind the block's tables
+                    entering = false;
+                    if (sg.symbol_bit < br.consumed()) {
+                        st = MD2_PNG_ST_INDEX;
+                        break;
+                    }
+                    br.seek_bit(sg.symbol_bit);
+                }
+            }
             while (true) {
                 br.refill();
+                if constexpr (M == kIndex) ix.candidate(header, br.consumed(), pos, lane);   // a symbol's start
+                if constexpr (M == kSegment) {
+                    if (pos - sg.start >= sg.segment_bytes) {
+                        st = MD2_PNG_ST_INDEX;
+                        break;
+                    }
+                }
                 int sym = decode(lit, br);
                 if (sym < 0) {
                     st = br.no_code();
                     break;
                 }
                 if (sym < 256) {
-                    if (lane == 0) ring[pos & kRingMask] = (uint8_t)sym;
+                    if constexpr (M == kRun) {
+                        if (lane == 0) ring[pos & kRingMask] = (uint8_t)sym;
+                    } else if constexpr (M == kSegment) {
+                        if (lane == 0) seg[pos - sg.start] = (uint16_t)sym;
+                    }
                     ++pos;
                 } else if (sym == 256) {
                     break;
@@ -407,34 +553,280 @@ __global__ __launch_bounds__(kWave) void png_inflate_kernel(const uint8_t* __res
                         st = MD2_PNG_ST_DIST;
                         break;
                     }
-                    if (len > total - pos) len = total - pos;
-                    const uint32_t from = pos - dist;
-                    wave_sync();
-                    if (dist >= len) {
-                        for (uint32_t i = lane; i < len; i += kWave)
-                            ring[(pos + i) & kRingMask] = ring[(from + i) & kRingMask];
-                    } else {   // the copy repeats a period: byte i is source byte i mod dist
-                        for (uint32_t i = lane; i < len; i += kWave)
-                            ring[(pos + i) & kRingMask] = ring[(from + i % dist) & kRingMask];
+                    if (len > limit - pos) {
+                        len = limit - pos;
+                        if constexpr (M == kSegment)
+                            if (!sg.last) st = MD2_PNG_ST_INDEX;   // a true entry lies between two symbols
                     }
-                    wave_sync();
+                    const uint32_t from = pos - dist;
+                    if constexpr (M == kRun) {
+                        wave_sync();
+                        if (dist >= len) {
+                            for (uint32_t i = lane; i < len; i += kWave)
+                                ring[(pos + i) & kRingMask] = ring[(from + i) & kRingMask];
+                        } else {   // the copy repeats a period: byte i is source byte i mod dist
+                            for (uint32_t i = lane; i < len; i += kWave)
+                                ring[(pos + i) & kRingMask] = ring[(from + i % dist) & kRingMask];
+                        }
+                        wave_sync();
+                    } else if constexpr (M == kSegment) {
+                        // a source inside the segment is copied as the symbol it is (a marker stays a
+                        // marker); one before it becomes 0x8000 | k: the byte k + 1 before the start
+                        wave_sync();
+                        for (uint32_t i = lane; i < len; i += kWave) {
+                            const uint32_t q = from + (dist >= len ? i : i % dist);
+                            seg[pos - sg.start + i] =
+                                q >= sg.start ? seg[q - sg.start] : (uint16_t)(0x8000u | (sg.start - 1 - q));
+                        }
+                        wave_sync();
+                    }
                     pos += len;
+                    if constexpr (M == kSegment)
+                        if (st) break;
                 }
-                if (pos >= total || br.overrun()) break;
-                if (pos - flushed >= kFlush) flush(pos & ~15u);
+                if constexpr (M == kSegment) {
+                    if (pos >= limit && !sg.last && !br.overrun()) {   // the next symbol's start is the candidate
+                        sg.exit_header = header;
+                        sg.exit_symbol = br.consumed();
+                        stopped = true;
+                        break;
+                    }
+                }
+                if (pos >= limit || br.overrun()) break;
+                if constexpr (M == kRun)
+                    if (pos - flushed >= kFlush) flush(pos & ~15u);
             }
             if (st) break;
+            if constexpr (M == kSegment)
+                if (stopped) break;
         }
-        if (pos >= total || br.overrun()) break;
+        if constexpr (M == kSegment) {   // a block that ends at the limit: the next header is the candidate
+            if ((pos >= limit && sg.last) || br.overrun()) break;
+        } else {
+            if (pos >= limit || br.overrun()) break;
+        }
         if (last) {
             st = MD2_PNG_ST_END;   // the last block ends before the image is complete
             break;
         }
-        if (pos - flushed >= kFlush) flush(pos & ~15u);
+        if constexpr (M == kRun)
+            if (pos - flushed >= kFlush) flush(pos & ~15u);
     }
     if (br.overrun()) st = MD2_PNG_ST_END;   // whatever the zeros past the end decoded to
-    flush((uint32_t)align16(pos));
+    if constexpr (M == kRun) flush((uint32_t)align16(pos));
+    if constexpr (M == kSegment)
+        if (!st && !sg.last && !stopped) st = MD2_PNG_ST_INDEX;
+    return st;
+}
+
+__global__ __launch_bounds__(kWave) void png_inflate_kernel(const uint8_t* __restrict__ streams,
+                                                            const md2_png_image* __restrict__ images,
+                                                            uint8_t* __restrict__ workspace,
+                                                            uint32_t* __restrict__ status) {
+    __shared__ __attribute__((aligned(16))) uint8_t ring[kRing];
+    __shared__ __attribute__((aligned(16))) uint32_t in[kInWords];
+    __shared__ Scratch sc;
+
+    const int img = blockIdx.x, lane = threadIdx.x;
+    const md2_png_image im = images[img];
+    const uint32_t total = (uint32_t)raw_bytes(im.height, im.width);
+    uint8_t* ws = workspace + workspace_offset(images, img, lane);
+
+    Reader br;
+    br.src = streams + im.stream_offset;
+    br.nbytes = im.stream_bytes;
+    br.in = in;
+    br.lane = lane;
+    Indexer ix{};
+    Segment sg{};
+    uint32_t pos;
+    const uint32_t st = inflate_walk<kRun>(br, sc, total, lane, ring, ws, ix, sg, pos);
     if (lane == 0) status[img] = st;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The indexed decoder (md2hot.h): the output of a stream is cut into segments of at least
+// segment_bytes bytes at boundary candidates; md2_png_index finds the cuts once with the serial
+// walk, md2_png_run_indexed then decodes every segment of every image at the same time.
+
+__host__ __device__ inline uint32_t seg_capacity(uint64_t raw, uint32_t segment_bytes) {
+    return (uint32_t)(raw / segment_bytes) + 1;
+}
+__host__ __device__ inline uint64_t index_size(uint64_t raw, uint32_t segment_bytes) {
+    return align16(kIndexHeader + (uint64_t)sizeof(IndexEntry) * seg_capacity(raw, segment_bytes));
+}
+
+// Where image `img`'s status words start among the per-segment words: the capacities before it.
+__device__ inline uint32_t capacity_offset(const md2_png_image* images, int img, uint32_t segment_bytes, int lane) {
+    uint32_t sum = 0;
+    for (int i = lane; i < img; i += kWave)
+        sum += seg_capacity(raw_bytes(images[i].height, images[i].width), segment_bytes);
+    for (int d = kWave / 2; d > 0; d >>= 1) sum += __shfl_xor(sum, d);
+    return uniform(sum);
+}
+
+__global__ __launch_bounds__(kWave) void png_index_kernel(const uint8_t* __restrict__ streams,
+                                                          const md2_png_image* __restrict__ images,
+                                                          uint32_t segment_bytes, uint8_t* __restrict__ index,
+                                                          const uint64_t* __restrict__ index_offsets,
+                                                          uint32_t* __restrict__ status) {
+    __shared__ __attribute__((aligned(16))) uint32_t in[kInWords];
+    __shared__ Scratch sc;
+
+    const int img = blockIdx.x, lane = threadIdx.x;
+    const md2_png_image im = images[img];
+    const uint32_t total = (uint32_t)raw_bytes(im.height, im.width);
+    uint8_t* base = index + index_offsets[img];
+
+    Reader br;
+    br.src = streams + im.stream_offset;
+    br.nbytes = im.stream_bytes;
+    br.in = in;
+    br.lane = lane;
+    Indexer ix;
+    ix.entries = reinterpret_cast<IndexEntry*>(base + kIndexHeader);
+    ix.cap = seg_capacity(total, segment_bytes);
+    ix.count = 1;   // segment 0: bit 0, output 0
+    ix.seg_start = 0;
+    ix.segment_bytes = segment_bytes;
+    if (lane == 0) {
+        IndexEntry e = {0, 0, 0, 0};
+        ix.entries[0] = e;
+    }
+    Segment sg{};
+    uint32_t pos;
+    const uint32_t st = inflate_walk<kIndex>(br, sc, total, lane, nullptr, nullptr, ix, sg, pos);
+    // a stream that did not inflate gets an index nothing can be decoded from: count 0
+    const uint32_t count = (st || ix.count > ix.cap) ? 0 : ix.count;
+    if (lane == 0) {
+        uint32_t* head = reinterpret_cast<uint32_t*>(base);
+        head[0] = count;
+        head[1] = segment_bytes;
+        head[2] = head[3] = 0;
+        status[img] = st;
+    }
+    const uint32_t end = (uint32_t)index_size(total, segment_bytes);
+    for (uint32_t o = kIndexHeader + (uint32_t)sizeof(IndexEntry) * count + 4u * lane; o < end; o += 4u * kWave)
+        *reinterpret_cast<uint32_t*>(base + o) = 0;
+}
+
+// One wave per (image, segment).  Writes the segment's symbols at symbols[p] for the positions p
+// of its own range [out_pos, next out_pos) and nothing else but its own status word.
+template <int S>
+__global__ __launch_bounds__(kWave) void png_segment_kernel(const uint8_t* __restrict__ streams,
+                                                            const md2_png_image* __restrict__ images,
+                                                            const uint64_t* __restrict__ index_offsets,
+                                                            uint16_t* __restrict__ symbols,
+                                                            uint32_t* __restrict__ seg_status) {
+    __shared__ __attribute__((aligned(16))) uint16_t seg[S + kMaxSymbol + 6];   // S + 257 positions are enough
+    __shared__ __attribute__((aligned(16))) uint32_t in[kInWords];
+    __shared__ Scratch sc;
+
+    const int img = blockIdx.y, lane = threadIdx.x;
+    const uint32_t s = blockIdx.x;
+    const md2_png_image im = images[img];
+    const uint32_t total = (uint32_t)raw_bytes(im.height, im.width);
+    const uint32_t cap = seg_capacity(total, S);
+    if (s >= cap) return;   // the grid is as wide as the batch's largest image
+    uint32_t* word = seg_status + capacity_offset(images, img, S, lane) + s;
+    const uint8_t* ix = streams + index_offsets[img];
+    const uint32_t count = reinterpret_cast<const uint32_t*>(ix)[0];
+    const uint32_t stored_s = reinterpret_cast<const uint32_t*>(ix)[1];
+    if (count < 1 || count > cap || stored_s != (uint32_t)S) {   // segment 0 speaks for the image
+        if (lane == 0) *word = s == 0 ? MD2_PNG_ST_INDEX : 0;
+        return;
+    }
+    if (s >= count) {
+        if (lane == 0) *word = 0;
+        return;
+    }
+    const IndexEntry* entries = reinterpret_cast<const IndexEntry*>(ix + kIndexHeader);
+    const IndexEntry e = entries[s];
+    IndexEntry next = e;
+    Segment sg;
+    sg.last = s == count - 1;
+    if (!sg.last) next = entries[s + 1];
+    sg.header_bit = e.header_bit;
+    sg.symbol_bit = e.symbol_bit;
+    sg.start = e.out_pos;
+    sg.limit = sg.last ? total : next.out_pos;
+    sg.segment_bytes = S;
+    sg.exit_header = sg.exit_symbol = 0;
+
+    uint32_t st = 0, pos = 0;
+    if (e.header_bit > e.symbol_bit || e.symbol_bit > 8ull * im.stream_bytes || (s == 0 && (e.out_pos | e.header_bit | e.symbol_bit) != 0) ||
+        sg.start >= sg.limit || sg.limit > total || sg.limit - sg.start > (uint32_t)S + kMaxSymbol - 1)
+        st = MD2_PNG_ST_INDEX;
+    if (!st) {
+        Reader br;
+        br.src = streams + im.stream_offset;
+        br.nbytes = im.stream_bytes;
+        br.in = in;
+        br.lane = lane;
+        Indexer none{};
+        st = inflate_walk<kSegment>(br, sc, total, lane, seg, nullptr, none, sg, pos);
+        if (!st && (pos != sg.limit || (!sg.last && (sg.exit_header != next.header_bit ||
+                                                     sg.exit_symbol != next.symbol_bit))))
+            st = MD2_PNG_ST_INDEX;
+    }
+    if (!st) {
+        wave_sync();
+        uint16_t* dstp = symbols + workspace_offset(images, img, lane) + sg.start;
+        const uint32_t n = sg.limit - sg.start;
+        for (uint32_t i = lane; i < n; i += kWave) dstp[i] = seg[i];
+    }
+    if (lane == 0) *word = st;
+}
+
+constexpr int kResolveThreads = 256;
+
+// One workgroup per image: ORs the image's segment words into its status word and, if that is
+// 0, turns the symbols into the scanline bytes segment after segment.  A marker of segment j
+// reads a byte before the segment's start, which an earlier round of this workgroup wrote.
+__global__ __launch_bounds__(kResolveThreads) void png_resolve_kernel(const uint8_t* __restrict__ streams,
+                                                                      const md2_png_image* __restrict__ images,
+                                                                      const uint64_t* __restrict__ index_offsets,
+                                                                      uint32_t segment_bytes, uint8_t* workspace,
+                                                                      const uint16_t* __restrict__ symbols,
+                                                                      const uint32_t* __restrict__ seg_status,
+                                                                      uint32_t* __restrict__ status) {
+    __shared__ uint32_t bits;
+    const int img = blockIdx.x, tid = threadIdx.x, lane = tid & (kWave - 1);
+    const md2_png_image im = images[img];
+    const uint32_t total = (uint32_t)raw_bytes(im.height, im.width);
+    const uint32_t cap = seg_capacity(total, segment_bytes);
+    const uint32_t* words = seg_status + capacity_offset(images, img, segment_bytes, lane);
+    uint32_t mine = 0;
+    for (uint32_t j = tid; j < cap; j += kResolveThreads) mine |= words[j];
+    if (tid == 0) bits = 0;
+    __syncthreads();
+    if (mine) atomicOr(&bits, mine);   // an integer OR in LDS: the order does not matter
+    __syncthreads();
+    const uint32_t st = bits;
+    if (tid == 0) status[img] = st;
+    if (st) return;   // the scanlines are not complete: nothing is resolved, nothing unfiltered
+
+    // every segment wave found its entry and the next consistent: the entries cover [0, total)
+    const uint64_t off = workspace_offset(images, img, lane);
+    uint8_t* ws = workspace + off;
+    const uint16_t* sym = symbols + off;
+    const uint8_t* ix = streams + index_offsets[img];
+    const uint32_t count = reinterpret_cast<const uint32_t*>(ix)[0];
+    const IndexEntry* entries = reinterpret_cast<const IndexEntry*>(ix + kIndexHeader);
+    uint32_t start = 0;
+    for (uint32_t j = 0; j < count; ++j) {
+        const uint32_t end = j + 1 < count ? entries[j + 1].out_pos : total;
+        for (uint32_t p = start + tid; p < end; p += kResolveThreads) {
+            const uint32_t v = sym[p];
+            ws[p] = (v & 0x8000u) ? ws[start - 1 - (v & 0x7FFFu)] : (uint8_t)v;
+        }
+        // segment j is final before segment j + 1 reads it: the workgroup's own writes, made
+        // visible to the workgroup, behind the workgroup's own barrier
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __syncthreads();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        start = end;
+    }
 }
 
 __device__ inline int paeth(int a, int b, int c) {
@@ -551,12 +943,15 @@ const char* check_images(const md2_png_image* images, int n) {
     return nullptr;
 }
 
-const char* check_ranges(const md2_png_image* images, int n, uint64_t streams_bytes, uint64_t out_bytes) {
+const char* check_ranges(const md2_png_image* images, int n, uint64_t streams_bytes, uint64_t out_bytes,
+                         bool with_out = true) {
     for (int i = 0; i < n; ++i) {
         const md2_png_image& im = images[i];
-        if (im.stream_offset % 16 || im.out_offset % 16) return "png: stream_offset and out_offset must be multiples of 16";
+        if (im.stream_offset % 16 || (with_out && im.out_offset % 16))
+            return "png: stream_offset and out_offset must be multiples of 16";
         if (im.stream_offset > streams_bytes || im.stream_bytes > streams_bytes - im.stream_offset)
             return "png: a stream reaches past streams_bytes";
+        if (!with_out) continue;
         const uint64_t ob = (uint64_t)im.height * im.width * 3;
         if (im.out_offset > out_bytes || ob > out_bytes - im.out_offset) return "png: a frame reaches past out_bytes";
     }
@@ -569,9 +964,142 @@ size_t workspace_need(const md2_png_image* images, int n) {
     return total;
 }
 
+const char* check_segment_bytes(int segment_bytes) {
+    if (segment_bytes < 1024 || segment_bytes > 32768 || (segment_bytes & (segment_bytes - 1)))
+        return "png: segment_bytes must be a power of two in 1024..32768";
+    return nullptr;
+}
+
+// every image's index lies, 16-byte aligned, inside a buffer of `bytes` bytes (`past`: what to say if not)
+const char* check_index(const md2_png_image* images, const uint64_t* index_offsets, int n, int segment_bytes,
+                        uint64_t bytes, const char* past) {
+    for (int i = 0; i < n; ++i) {
+        if (index_offsets[i] % 16) return "png: an index offset must be a multiple of 16";
+        const uint64_t ib = index_size(raw_bytes(images[i].height, images[i].width), segment_bytes);
+        if (index_offsets[i] > bytes || ib > bytes - index_offsets[i]) return past;
+    }
+    return nullptr;
+}
+
+size_t indexed_workspace_need(const md2_png_image* images, int n, int segment_bytes) {
+    uint64_t words = 0;
+    for (int i = 0; i < n; ++i) words += seg_capacity(raw_bytes(images[i].height, images[i].width), segment_bytes);
+    return 3 * workspace_need(images, n) + align16(4 * words);
+}
+
+template <int S>
+void launch_segments(dim3 grid, hipStream_t st, const uint8_t* streams, const md2_png_image* dev_images,
+                     const uint64_t* dev_index_offsets, uint16_t* symbols, uint32_t* seg_status) {
+    hipLaunchKernelGGL(png_segment_kernel<S>, grid, dim3(kWave), 0, st, streams, dev_images, dev_index_offsets, symbols,
+                       seg_status);
+}
+
 }  // namespace
 
 extern "C" {
+
+size_t md2_png_index_bytes(int height, int width, int segment_bytes) {
+    const char* msg = check_segment_bytes(segment_bytes);
+    if (!msg && (height < 1 || height > kMaxDim || width < 1 || width > kMaxDim))
+        msg = "png: height and width must be 1..8192";
+    if (msg) {
+        md2_report_error(MD2_ERR_ARG, msg);
+        return 0;
+    }
+    return index_size(raw_bytes(height, width), segment_bytes);
+}
+
+size_t md2_png_indexed_workspace_bytes(const md2_png_image* images, int n, int segment_bytes) {
+    const char* msg = check_images(images, n);
+    if (!msg) msg = check_segment_bytes(segment_bytes);
+    if (msg) {
+        md2_report_error(MD2_ERR_ARG, msg);
+        return 0;
+    }
+    return indexed_workspace_need(images, n, segment_bytes);
+}
+
+int md2_png_index(const uint8_t* streams, uint64_t streams_bytes, const md2_png_image* images,
+                  const md2_png_image* dev_images, int n, int segment_bytes, uint8_t* index, uint64_t index_bytes,
+                  const uint64_t* index_offsets, const uint64_t* dev_index_offsets, uint32_t* status, void* stream) {
+    if (const char* msg = check_images(images, n)) return md2_report_error(MD2_ERR_ARG, msg);
+    if (const char* msg = check_segment_bytes(segment_bytes)) return md2_report_error(MD2_ERR_ARG, msg);
+    if (n == 0) return MD2_OK;
+    if (!streams || !dev_images || !index || !index_offsets || !dev_index_offsets || !status)
+        return md2_report_error(MD2_ERR_ARG,
+                                "png: streams/dev_images/index/index_offsets/dev_index_offsets/status is NULL");
+    if (const char* msg = check_ranges(images, n, streams_bytes, ~(uint64_t)0, false))
+        return md2_report_error(MD2_ERR_ARG, msg);
+    if (const char* msg = check_index(images, index_offsets, n, segment_bytes, index_bytes,
+                                      "png: an index reaches past index_bytes"))
+        return md2_report_error(MD2_ERR_ARG, msg);
+    if (reinterpret_cast<uintptr_t>(streams) % 16 || reinterpret_cast<uintptr_t>(index) % 16 ||
+        reinterpret_cast<uintptr_t>(dev_images) % 8 || reinterpret_cast<uintptr_t>(dev_index_offsets) % 8)
+        return md2_report_error(MD2_ERR_ARG,
+                                "png: streams and index must be 16-byte, dev_images and dev_index_offsets 8-byte aligned");
+    hipLaunchKernelGGL(png_index_kernel, dim3(n), dim3(kWave), 0, (hipStream_t)stream, streams, dev_images,
+                       (uint32_t)segment_bytes, index, dev_index_offsets, status);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? MD2_OK : md2_report_error(MD2_ERR_HIP, hipGetErrorString(e));
+}
+
+int md2_png_check_indexed(const md2_png_image* images, const uint64_t* index_offsets, int n, int segment_bytes,
+                          uint64_t streams_bytes, uint64_t out_bytes) {
+    if (const char* msg = check_images(images, n)) return md2_report_error(MD2_ERR_ARG, msg);
+    if (const char* msg = check_segment_bytes(segment_bytes)) return md2_report_error(MD2_ERR_ARG, msg);
+    if (n && !index_offsets) return md2_report_error(MD2_ERR_ARG, "png: index_offsets is NULL");
+    if (const char* msg = check_ranges(images, n, streams_bytes, out_bytes)) return md2_report_error(MD2_ERR_ARG, msg);
+    if (const char* msg = check_index(images, index_offsets, n, segment_bytes, streams_bytes,
+                                      "png: an index reaches past streams_bytes"))
+        return md2_report_error(MD2_ERR_ARG, msg);
+    return MD2_OK;
+}
+
+int md2_png_run_indexed(const uint8_t* streams, uint64_t streams_bytes, const md2_png_image* images,
+                        const md2_png_image* dev_images, const uint64_t* index_offsets,
+                        const uint64_t* dev_index_offsets, int n, int segment_bytes, uint8_t* workspace,
+                        size_t workspace_bytes, uint8_t* out, uint64_t out_bytes, uint32_t* status, void* stream) {
+    if (const char* msg = check_images(images, n)) return md2_report_error(MD2_ERR_ARG, msg);
+    if (const char* msg = check_segment_bytes(segment_bytes)) return md2_report_error(MD2_ERR_ARG, msg);
+    if (n == 0) return MD2_OK;
+    if (!streams || !dev_images || !index_offsets || !dev_index_offsets || !workspace || !out || !status)
+        return md2_report_error(
+            MD2_ERR_ARG, "png: streams/dev_images/index_offsets/dev_index_offsets/workspace/out/status is NULL");
+    if (const char* msg = check_ranges(images, n, streams_bytes, out_bytes)) return md2_report_error(MD2_ERR_ARG, msg);
+    if (const char* msg = check_index(images, index_offsets, n, segment_bytes, streams_bytes,
+                                      "png: an index reaches past streams_bytes"))
+        return md2_report_error(MD2_ERR_ARG, msg);
+    if (reinterpret_cast<uintptr_t>(streams) % 16 || reinterpret_cast<uintptr_t>(workspace) % 16 ||
+        reinterpret_cast<uintptr_t>(dev_images) % 8 || reinterpret_cast<uintptr_t>(dev_index_offsets) % 8)
+        return md2_report_error(
+            MD2_ERR_ARG,
+            "png: streams and workspace must be 16-byte, dev_images and dev_index_offsets 8-byte aligned");
+    if (indexed_workspace_need(images, n, segment_bytes) > workspace_bytes)
+        return md2_report_error(MD2_ERR_ARG, "png: the batch needs more workspace than workspace_bytes");
+    const size_t scan = workspace_need(images, n);
+    uint16_t* symbols = reinterpret_cast<uint16_t*>(workspace + scan);
+    uint32_t* seg_status = reinterpret_cast<uint32_t*>(workspace + 3 * scan);
+    uint32_t widest = 1;
+    for (int i = 0; i < n; ++i) {
+        const uint32_t c = seg_capacity(raw_bytes(images[i].height, images[i].width), segment_bytes);
+        widest = c > widest ? c : widest;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(widest, n);
+    switch (segment_bytes) {
+        case 1024: launch_segments<1024>(grid, st, streams, dev_images, dev_index_offsets, symbols, seg_status); break;
+        case 2048: launch_segments<2048>(grid, st, streams, dev_images, dev_index_offsets, symbols, seg_status); break;
+        case 4096: launch_segments<4096>(grid, st, streams, dev_images, dev_index_offsets, symbols, seg_status); break;
+        case 8192: launch_segments<8192>(grid, st, streams, dev_images, dev_index_offsets, symbols, seg_status); break;
+        case 16384: launch_segments<16384>(grid, st, streams, dev_images, dev_index_offsets, symbols, seg_status); break;
+        default: launch_segments<32768>(grid, st, streams, dev_images, dev_index_offsets, symbols, seg_status); break;
+    }
+    hipLaunchKernelGGL(png_resolve_kernel, dim3(n), dim3(kResolveThreads), 0, st, streams, dev_images,
+                       dev_index_offsets, (uint32_t)segment_bytes, workspace, symbols, seg_status, status);
+    hipLaunchKernelGGL(png_unfilter_kernel, dim3(n), dim3(kWave), 0, st, streams, dev_images, workspace, out, status);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? MD2_OK : md2_report_error(MD2_ERR_HIP, hipGetErrorString(e));
+}
 
 size_t md2_png_workspace_bytes(const md2_png_image* images, int n) {
     if (const char* msg = check_images(images, n)) {

@@ -44,7 +44,8 @@ way: a file `jpeg_ops.parse_jpeg` refuses is offered to `png_ops.parse_png`, the
 streams get a region of their own in the staging block behind the JPEG one, `md2_png_run`
 inflates and unfilters them into the ragged buffer, and their status words follow the JPEG
 streams' through the same pinned copy.  Gray, palette, alpha, 16-bit and interlaced files stay
-with PIL (`pil_fallbacks` counts the frames PIL decoded).  Packs hold no PNG streams.
+with PIL (`pil_fallbacks` counts the frames PIL decoded).  A pack's PNG records need no flag:
+they carry a segment index and go through `md2_png_run_indexed`.
 
 `pack=FramePack(...)` (pack.py) feeds the same device decoder from a packed
 frame file instead of the image files: sizes come from the pack's records and no file is
@@ -70,7 +71,7 @@ import torch
 from . import _lib, jpeg_ops, png_ops
 from .augment import GpuAugmentMixed
 from .datasets import item_seed
-from .pack import KIND_JPEG, frame_key
+from .pack import KIND_JPEG, KIND_PNG, frame_key
 
 ALIGN = 256        # frame offsets in the ragged buffer
 MAX_THREADS = 16   # decoding threads, whatever --num_workers asks for
@@ -109,6 +110,8 @@ class _StagedPng:
 
     def __init__(self, images, n, offset, base, total):
         self.images, self.n, self.offset, self.base, self.total = images, n, offset, base, total
+        self.index_offsets = None   # a packed batch: where each stream's index lies, for md2_png_run_indexed
+        self.segment_bytes = 0      # ... and the segment_bytes of the pack's indexes
 
 
 class BatchLoader:
@@ -350,9 +353,31 @@ class BatchLoader:
             jpeg_ops.check_described_indexed(images, index_offsets, nj, len(quant), len(huff), jtotal - base,
                                              frames_total)
         reads = [(row, base + o, b) for row, o, b in reads]
-        pos, pil = jtotal, []
+        pos, pil, png = jtotal, [], None
+        as_png = [n for n in range(F * B) if recs["kind"][rows[n]] == KIND_PNG]
+        if as_png:   # their own region behind the JPEG one: the image array, the index offsets, the records
+            pos = (pos + ALIGN - 1) // ALIGN * ALIGN
+            npng = len(as_png)
+            pimages = (_lib.PngImage * npng)()
+            pindex = (ctypes.c_uint64 * npng)()
+            pbase = (npng * (png_ops.IMAGE_BYTES + 8) + 15) // 16 * 16
+            o = 0
+            for i, n in enumerate(as_png):
+                r = recs[rows[n]]
+                im = pimages[i]
+                im.height, im.width, im.out_offset = int(r["height"]), int(r["width"]), offsets[n]
+                im.stream_offset, im.stream_bytes = o, int(r["stream_bytes"])
+                pindex[i] = o + (im.stream_bytes + 15) // 16 * 16
+                reads.append((rows[n], pos + pbase + o, int(r["data_bytes"])))   # one preadv: the index behind the stream
+                o += (int(r["data_bytes"]) + 15) // 16 * 16
+            ptotal = pbase + max(o, 16)
+            png_ops.check_png_described_indexed(pimages, pindex, npng, pack.png_segment_bytes, ptotal - pbase,
+                                                frames_total)
+            png = _StagedPng(pimages, npng, pos, pbase, ptotal)
+            png.index_offsets, png.segment_bytes = pindex, pack.png_segment_bytes
+            pos += ptotal
         for n in range(F * B):
-            if recs["kind"][rows[n]] != KIND_JPEG:
+            if recs["kind"][rows[n]] not in (KIND_JPEG, KIND_PNG):
                 pos = (pos + ALIGN - 1) // ALIGN * ALIGN
                 size = int(recs["data_bytes"][rows[n]])
                 pil.append((n, pos, size))
@@ -367,11 +392,19 @@ class BatchLoader:
         if nj:
             host[:nq] = pack.quant[list(quant)].reshape(-1)
             host[nq:nq + nh] = pack.huff[list(huff)].reshape(-1)
+        if png is not None:
+            nb = png.n * png_ops.IMAGE_BYTES
+            head = host[png.offset:png.offset + png.base]
+            head[:nb] = np.frombuffer(png.images, np.uint8, nb)
+            head[nb:nb + 8 * png.n] = np.frombuffer(png.index_offsets, np.uint8, 8 * png.n)
+            head[nb + 8 * png.n:] = 0
         self._map(lambda rd: pack.read_into(rd[0], host[rd[1]:rd[1] + rd[2]]), reads)
         names = [(items[n % B].index, items[n % B].line, items[n % B].paths[n // B], "jpeg") for n in on_device]
+        names += [(items[n % B].index, items[n % B].line, items[n % B].paths[n // B], "png") for n in as_png]
         st = _Staged(slot, total, offsets, items, spill)
         st.jpeg = _StagedJpeg(images, nj, len(quant), len(huff), base, jtotal, pil, frames_total, names)
         st.jpeg.index_offsets = index_offsets
+        st.jpeg.png = png
         return st
 
     def _reserve(self, slot: int, total: int):
@@ -425,8 +458,12 @@ class BatchLoader:
             host[:j.n].copy_(status, non_blocking=True)
         if j.png is not None:
             p = j.png
-            status = png_ops.run_png_staged(up[p.offset:p.offset + p.total], p.images, p.n, p.base, p.total, frames,
-                                            self.device)
+            if p.index_offsets is not None:
+                status = png_ops.run_png_staged_indexed(up[p.offset:p.offset + p.total], p.images, p.index_offsets,
+                                                        p.n, p.base, p.total, p.segment_bytes, frames, self.device)
+            else:
+                status = png_ops.run_png_staged(up[p.offset:p.offset + p.total], p.images, p.n, p.base, p.total,
+                                                frames, self.device)
             host[j.n:words].copy_(status, non_blocking=True)
         for n, o, size in j.pil:
             frames[st.offsets[n]:st.offsets[n] + size].copy_(up[o:o + size], non_blocking=True)

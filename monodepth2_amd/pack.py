@@ -12,7 +12,12 @@ sampling)` such a file is instead encoded as baseline JPEG on the device (jpeg_o
 encode_jpeg_batch) and stored as a JPEG record under its own key: a fraction of the size and
 decoded by the device decoder like the rest, but lossy; a batch from such a pack is bit-equal
 to the batch from the tree after `convert_dataset` with the same quality and sampling, read
-as .jpg with --device_decode.  `FramePack` opens such
+as .jpg with --device_decode.  With `png_records=True` an 8-bit RGB PNG file is instead kept
+as it is, lossless and at the file's own size: a PNG record holds its deflate stream
+(png_ops.parse_png) and, directly behind it, the stream's segment index
+(png_ops.index_png_batch: where every segment of `segment_bytes` output bytes starts, found
+once on the device), and the loader decodes it with md2_png_run_indexed; a
+batch from such a pack is bit-equal to the batch from the tree.  `FramePack` opens such
 a file; `loader.BatchLoader(pack=...)` then feeds the step with an index lookup and one
 `os.preadv` per frame, straight into pinned memory.
 
@@ -26,10 +31,15 @@ last, so a build that died leaves no magic):
             (stream_bytes), zeros to 16, then its index (nsub u64 states, nsub u32
             first_blocks, zeros to 16; nsub = max(ceil(8 * stream_bytes / 1024), 1)).
             RAW: height * width * 3 bytes of RGB.
+            PNG: the deflate stream with its 4 trailer bytes (stream_bytes), zeros to 16,
+            then its index (include/md2hot.h): u32 count, u32 segment_bytes, 8 zero bytes,
+            height * (1 + 3 width) // segment_bytes + 1 entries of u64 header_bit, u64
+            symbol_bit, u32 out_pos, u32 0 (the first `count` in use, the rest zero), zeros
+            to 16: png_ops.index_nbytes(height, width, segment_bytes), fixed per geometry.
   quant     num_quant tables of 64 u16 in natural order   } the layout of md2_jpeg_bank:
   huff      num_huff tables of 16 counts + 256 values     } a batch's bank is a gather by id
-  records   num_records x 96 bytes, sorted by name: u32 kind (0 JPEG, 1 RAW), height, width,
-            sampling; u64 data_offset, data_bytes; u32 stream_bytes, name_offset, name_bytes;
+  records   num_records x 96 bytes, sorted by name: u32 kind (0 JPEG, 1 RAW, 2 PNG), height, width,
+            sampling (a PNG record: its index's segment_bytes; its table ids are zero); u64 data_offset, data_bytes; u32 stream_bytes, name_offset, name_bytes;
             u32 quant[3], dc[3], ac[3] (table ids); 16 reserved bytes: byte 0 = 1 and byte
             1 = the quality for a frame transcoded from a lossless file, else zeros (readers
             ignore them when decoding)
@@ -54,7 +64,7 @@ from ._lib import JPEG_HUFF_BYTES, JPEG_QUANT_BYTES
 MAGIC = b"MD2PACK\0"
 VERSION = 1
 HEADER_BYTES = 128
-KIND_JPEG, KIND_RAW = 0, 1
+KIND_JPEG, KIND_RAW, KIND_PNG = 0, 1, 2
 _HEADER = struct.Struct("<8sIIQQIIQQQQQQ")
 RECORD = np.dtype([("kind", "<u4"), ("height", "<u4"), ("width", "<u4"), ("sampling", "<u4"),
                    ("data_offset", "<u8"), ("data_bytes", "<u8"),
@@ -80,7 +90,9 @@ def frame_key(path: str, data_path: str) -> str:
 
 class PackRecord:
     """One frame on its way into a pack.  JPEG: `stream` (a jpeg_ops.JpegStream) and `index`
-    (its index bytes, jpeg_ops.index_jpeg_batch's or pack_index's).  RAW: `raw`, the decoded
+    (its index bytes, jpeg_ops.index_jpeg_batch's or pack_index's).  PNG: `stream` (a
+    png_ops.PngStream) and `index` (png_ops.index_png_batch's; its segment_bytes is read
+    from it).  RAW: `raw`, the decoded
     (h, w, 3) uint8 RGB frame.  `transcoded`: the quality a lossless file was encoded with on
     its way in (0: the stream is the file's own)."""
     __slots__ = ("name", "stream", "index", "raw", "transcoded")
@@ -88,7 +100,15 @@ class PackRecord:
     def __init__(self, name: str, stream=None, index=None, raw=None, transcoded: int = 0):
         if (stream is None) == (raw is None):
             raise ValueError(f"{name}: a record is either a stream with its index or raw RGB")
-        if stream is not None:
+        if isinstance(stream, png_ops.PngStream):
+            index = np.ascontiguousarray(index, dtype=np.uint8).reshape(-1)
+            if index.size < 16:
+                raise ValueError(f"{name}: an index of {index.size} bytes: a PNG index starts with 16 header bytes")
+            want = png_ops.index_nbytes(stream.height, stream.width, png_ops.index_segment_bytes(index))
+            if index.size != want:
+                raise ValueError(f"{name}: an index of {index.size} bytes for a {stream.height} x {stream.width} "
+                                 f"frame (expected {want} at segment_bytes {png_ops.index_segment_bytes(index)})")
+        elif stream is not None:
             index = np.ascontiguousarray(index, dtype=np.uint8).reshape(-1)
             if index.size != jpeg_ops.index_nbytes(len(stream.data)):
                 raise ValueError(f"{name}: an index of {index.size} bytes for a stream of {len(stream.data)} bytes "
@@ -97,7 +117,8 @@ class PackRecord:
             raw = np.ascontiguousarray(raw, dtype=np.uint8)
             if raw.ndim != 3 or raw.shape[2] != 3:
                 raise ValueError(f"{name}: raw frames are (h, w, 3) uint8, not {raw.shape}")
-        if transcoded and (stream is None or not 1 <= int(transcoded) <= 100):
+        if transcoded and (stream is None or isinstance(stream, png_ops.PngStream)
+                           or not 1 <= int(transcoded) <= 100):
             raise ValueError(f"{name}: a transcoded record is a stream with its quality, 1..100")
         self.name, self.stream, self.index, self.raw, self.transcoded = name, stream, index, raw, int(transcoded)
 
@@ -121,7 +142,16 @@ def write_pack(path: str, records: Iterable[PackRecord]) -> int:
             if rec.name in seen:
                 raise ValueError(f"{rec.name}: twice in one pack")
             seen.add(rec.name)
-            if rec.stream is not None:
+            if isinstance(rec.stream, png_ops.PngStream):
+                s = rec.stream
+                pad = _align16(len(s.data)) - len(s.data)
+                f.write(s.data)
+                f.write(b"\0" * pad)
+                f.write(rec.index.tobytes())
+                nbytes = len(s.data) + pad + rec.index.size
+                rows.append((rec.name, KIND_PNG, s.height, s.width, png_ops.index_segment_bytes(rec.index), pos, nbytes,
+                             len(s.data), [0] * 3, [0] * 3, [0] * 3, 0))
+            elif rec.stream is not None:
                 s = rec.stream
                 pad = _align16(len(s.data)) - len(s.data)
                 f.write(s.data)
@@ -212,10 +242,34 @@ class FramePack:
         if n:
             jpeg = r["kind"] == KIND_JPEG
             if (np.any(r["data_offset"] % 16) or np.any(r["data_offset"] < d_off)
-                    or np.any(r["data_offset"] + r["data_bytes"] > q_off) or np.any(r["kind"] > KIND_RAW)
+                    or np.any(r["data_offset"] + r["data_bytes"] > q_off) or np.any(r["kind"] > KIND_PNG)
                     or np.any(r["name_offset"].astype(np.uint64) + r["name_bytes"] > n_bytes)
                     or np.any(r["quant"][jpeg] >= nq) or np.any(r["dc"][jpeg] >= nh) or np.any(r["ac"][jpeg] >= nh)):
                 raise PackError(f"{self.path}: a record points outside its section")
+        # PNG records: one segment_bytes for the whole pack (a batch is one call), and every
+        # record as long as its stream and its geometry's index say
+        self.png_segment_bytes = 0
+        png = np.flatnonzero(r["kind"] == KIND_PNG) if n else []
+        if len(png):
+            sb = {int(x) for x in r["sampling"][png]}
+            try:
+                if len(sb) != 1:
+                    raise ValueError(f"PNG records with different segment_bytes {sorted(sb)}")
+                self.png_segment_bytes = png_ops.check_segment_bytes(sb.pop())
+                h, w = r["height"][png].astype(np.int64), r["width"][png].astype(np.int64)
+                if np.any(h < 1) or np.any(h > png_ops.MAX_DIM) or np.any(w < 1) or np.any(w > png_ops.MAX_DIM):
+                    raise ValueError(f"a PNG record's height or width is outside 1..{png_ops.MAX_DIM}")
+                sbytes = r["stream_bytes"][png].astype(np.int64)
+                entries = h * (1 + 3 * w) // self.png_segment_bytes + 1          # png_ops.index_nbytes, for all rows
+                want = (sbytes + 15) // 16 * 16 + (16 + 24 * entries + 15) // 16 * 16
+                wrong = np.flatnonzero((r["data_bytes"][png].astype(np.int64) != want) | (sbytes < 5))
+                if len(wrong):
+                    i = int(png[wrong[0]])
+                    raise ValueError(f"PNG record {i}: {int(r['data_bytes'][i])} data bytes, but its stream of "
+                                     f"{int(r['stream_bytes'][i])} bytes and the index of a {int(r['height'][i])} x "
+                                     f"{int(r['width'][i])} frame take {int(want[wrong[0]])}")
+            except ValueError as e:
+                raise PackError(f"{self.path}: {e}") from None
         self.names = [names[int(o):int(o) + int(b)].decode("utf-8") for o, b in zip(r["name_offset"], r["name_bytes"])]
         self._row = {name: i for i, name in enumerate(self.names)}
         # what the loader asks per frame, as plain Python values
@@ -268,7 +322,7 @@ class FramePack:
         """(JpegStream, index bytes) of a JPEG record, as write_pack took them."""
         rec = self.record(key)
         if rec["kind"] != KIND_JPEG:
-            raise ValueError(f"{key} is a RAW record")
+            raise ValueError(f"{key} is a {'PNG' if rec['kind'] == KIND_PNG else 'RAW'} record")
         data = self.read(key)
         n = int(rec["stream_bytes"])
         huff, dc, ac = {}, [], []
@@ -283,6 +337,15 @@ class FramePack:
         s = jpeg_ops.JpegStream(int(rec["height"]), int(rec["width"]), int(rec["sampling"]), factors, quant, huff,
                                 tuple(dc), tuple(ac), data[:n].tobytes())
         return s, data[_align16(n):].copy()
+
+    def png_stream(self, key: str):
+        """(PngStream, index bytes) of a PNG record, as write_pack took them."""
+        rec = self.record(key)
+        if rec["kind"] != KIND_PNG:
+            raise ValueError(f"{key} is a {'JPEG' if rec['kind'] == KIND_JPEG else 'RAW'} record")
+        data = self.read(key)
+        n = int(rec["stream_bytes"])
+        return png_ops.PngStream(int(rec["height"]), int(rec["width"]), data[:n].tobytes()), data[_align16(n):].copy()
 
     def missing(self, dataset) -> Optional[str]:
         """None if the pack holds every frame of every split line of `dataset`, else a
@@ -344,7 +407,8 @@ def frame_paths(data_path: str, line_lists: Sequence[Sequence[str]], dataset: st
 
 def records_from_files(paths: Dict[str, str], device=None, batch: int = 64, threads: int = 8,
                        transcode: Optional[Tuple[int, object]] = None,
-                       device_png: bool = False) -> Iterator[PackRecord]:
+                       device_png: bool = False, png_records: bool = False,
+                       segment_bytes: int = png_ops.SEGMENT_BYTES) -> Iterator[PackRecord]:
     """The records of the files {key: path}, in key order: read and parsed by `threads` host
     threads, the supported JPEG files indexed on the device `batch` at a time, every other
     file decoded with PIL into a RAW record.  transcode=(quality, sampling): such a file is
@@ -352,8 +416,15 @@ def records_from_files(paths: Dict[str, str], device=None, batch: int = 64, thre
     becomes a JPEG record under its own key, marked as transcoded.  With device_png as well,
     the PNG files png_ops.parse_png takes are not decoded by PIL: the device decodes them into
     a flat buffer that goes straight into the encoder (the same records, byte for byte).  RAW
-    records keep the PIL route: their frames have to be on the host anyway."""
-    on_device_png = bool(device_png) and transcode is not None
+    records keep the PIL route: their frames have to be on the host anyway.
+    png_records (not with transcode): a PNG file png_ops.parse_png takes becomes a PNG record,
+    its stream indexed on the device for segment_bytes with the rest of its batch and decoded
+    from that index once as a check; a file the parser, the indexer or that decode refuses
+    stays a RAW record through PIL."""
+    if png_records and transcode is not None:
+        raise ValueError("png_records and transcode exclude each other: a PNG file is either kept lossless as a "
+                         "PNG record or encoded as JPEG")
+    on_device_png = (bool(device_png) and transcode is not None) or bool(png_records)
 
     def load(key):
         path = paths[key]
@@ -375,7 +446,7 @@ def records_from_files(paths: Dict[str, str], device=None, batch: int = 64, thre
         for start in range(0, len(keys), batch):
             chunk = keys[start:start + batch]
             got = list(pool.map(load, chunk))
-            encoded = {}
+            encoded, png_kept = {}, {}
             if transcode is not None:
                 pngs = [n for n, g in enumerate(got) if isinstance(g, png_ops.PngStream)]
                 if pngs:
@@ -392,35 +463,77 @@ def records_from_files(paths: Dict[str, str], device=None, batch: int = 64, thre
                 for n, s in zip(lossless, streams):
                     got[n] = s
                     encoded[n] = int(transcode[0])
+            if png_records:
+                pngs = [n for n, g in enumerate(got) if isinstance(g, png_ops.PngStream)]
+                png_indexes = _checked_png_indexes([got[n] for n in pngs], segment_bytes, device) if pngs else []
+                for n, ix in zip(pngs, png_indexes):
+                    if ix is None:   # refused on the device: PIL's frame, as without the flag
+                        with Image.open(paths[chunk[n]]) as im:
+                            got[n] = np.asarray(im.convert("RGB"))
+                    else:
+                        png_kept[n] = ix
             on_device = [n for n, g in enumerate(got) if isinstance(g, jpeg_ops.JpegStream)]
             indexes = dict(zip(on_device, jpeg_ops.index_jpeg_batch([got[n] for n in on_device], device)))
             for n, key in enumerate(chunk):
-                if n in indexes:
+                if n in png_kept:
+                    yield PackRecord(key, stream=got[n], index=png_kept[n])
+                elif n in indexes:
                     yield PackRecord(key, stream=got[n], index=indexes[n], transcoded=encoded.get(n, 0))
                 else:
                     yield PackRecord(key, raw=got[n])
 
 
+def _checked_png_indexes(streams, segment_bytes: int, device) -> List[Optional[np.ndarray]]:
+    """index_png_batch's indexes, with None for a stream the indexer refuses or whose decode
+    from its index reports a bit (a wrong Adler-32, a bad filter byte)."""
+    import torch
+    indexes = png_ops.index_png_batch(streams, segment_bytes, device, check=False)
+    good = [i for i, ix in enumerate(indexes) if ix is not None]
+    if good:
+        offsets, pos = [], 0
+        for i in good:
+            offsets.append(pos)
+            pos += _align16(streams[i].height * streams[i].width * 3)
+        dev = torch.device(device) if device is not None else torch.device("cuda")
+        out = torch.empty(max(pos, 16), dtype=torch.uint8, device=dev)
+        words = png_ops.decode_png_batch_indexed([streams[i] for i in good], [indexes[i] for i in good], out, offsets,
+                                                 dev, segment_bytes=segment_bytes).cpu().tolist()
+        for i, w in zip(good, words):
+            if w:
+                indexes[i] = None
+    return indexes
+
+
 def build_pack(out: str, data_path: str, line_lists: Sequence[Sequence[str]], dataset: str = "kitti",
                png: bool = False, frame_ids: Sequence = (0, -1, 1), use_stereo: bool = False, device=None,
                batch: int = 64, threads: int = 8, transcode: Optional[Tuple[int, object]] = None,
-               device_png: bool = False) -> Dict:
+               device_png: bool = False, png_records: bool = False,
+               segment_bytes: int = png_ops.SEGMENT_BYTES) -> Dict:
     """Parse, index on the device, write: the frames the split lines of `line_lists` name
     under `data_path`, into the pack `out`.  Files are read by `threads` host threads and
     indexed `batch` at a time.  transcode=(quality, sampling): files the device decoder does
     not take are encoded as JPEG on the device instead of stored decoded (records_from_files);
-    device_png: the PNG files among them are decoded on the device too.
-    Returns {"frames", "jpeg", "raw", "transcoded", "pack_bytes", "file_bytes"} (file_bytes:
-    the size of the image files read; transcoded frames count as jpeg too)."""
+    device_png: the PNG files among them are decoded on the device too.  png_records (not
+    with transcode): 8-bit RGB PNG files are kept lossless as PNG records with a segment index
+    for segment_bytes.
+    Returns {"frames", "jpeg", "raw", "png", "transcoded", "pack_bytes", "file_bytes"}
+    (file_bytes: the size of the image files read; transcoded frames count as jpeg too)."""
+    if png_records and transcode is not None:
+        raise ValueError("png_records and transcode exclude each other: a PNG file is either kept lossless as a "
+                         "PNG record or encoded as JPEG")
+    if png_records:
+        png_ops.check_segment_bytes(segment_bytes)
     paths = frame_paths(data_path, line_lists, dataset, png, frame_ids, use_stereo)
-    stats = {"frames": 0, "jpeg": 0, "raw": 0, "transcoded": 0, "file_bytes": 0}
+    stats = {"frames": 0, "jpeg": 0, "raw": 0, "png": 0, "transcoded": 0, "file_bytes": 0}
     if transcode is not None:
         transcode = (int(transcode[0]), jpeg_ops.sampling_class(transcode[1]))
         jpeg_ops.quality_tables(transcode[0])
 
     def counted():
-        for rec in records_from_files(paths, device, batch, threads, transcode, device_png):
-            stats["jpeg" if rec.stream is not None else "raw"] += 1
+        for rec in records_from_files(paths, device, batch, threads, transcode, device_png, png_records,
+                                      segment_bytes):
+            stats["png" if isinstance(rec.stream, png_ops.PngStream) else
+                  "jpeg" if rec.stream is not None else "raw"] += 1
             stats["transcoded"] += 1 if rec.transcoded else 0
             stats["file_bytes"] += os.path.getsize(paths[rec.name])
             yield rec

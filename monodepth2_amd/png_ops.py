@@ -14,6 +14,13 @@ one pinned block and runs the decoder (inflate, then unfilter with the Adler-32 
 i lands in `out` as a tight (h, w, 3) image at byte `offsets[i]`, every byte equal to
 `np.asarray(Image.open(path).convert("RGB"))`.  There is no CPU path: a non-CUDA device is an
 error.
+
+The indexed decoder (`md2_png_run_indexed`) inflates the segments of a stream
+at the same time from an index of where they start.  `index_png_batch(streams, segment_bytes)`
+finds the indexes on the device (once: a frame pack keeps them behind the streams),
+`index_nbytes(h, w, segment_bytes)` is an index's size (fixed per geometry), and
+`decode_png_batch_indexed(streams, indexes, out, offsets)` is `decode_png_batch` from them:
+the same bytes and status words, or `_lib.PNG_ST_INDEX` for an index that does not fit.
 """
 from __future__ import annotations
 
@@ -36,7 +43,9 @@ STATUS_NAMES = ((_lib.PNG_ST_BLOCK, "a block type or stored length zlib refuses"
                 (_lib.PNG_ST_END, "the stream ends before the image is complete"),
                 (_lib.PNG_ST_DIST, "a match distance before the first byte"),
                 (_lib.PNG_ST_FILTER, "a filter byte above 4"),
-                (_lib.PNG_ST_ADLER, "the Adler-32 trailer does not fit the scanlines"))
+                (_lib.PNG_ST_ADLER, "the Adler-32 trailer does not fit the scanlines"),
+                (_lib.PNG_ST_INDEX, "the segment index does not fit the stream"))
+SEGMENT_BYTES = 16384   # the default S of an index
 
 
 def status_text(word: int) -> str:
@@ -163,6 +172,72 @@ def check_png_described(images, n: int, streams_bytes: int, out_bytes: int):
     _lib.check(_lib.lib().md2_png_check(images, n, streams_bytes, out_bytes), "md2_png_check")
 
 
+def check_segment_bytes(segment_bytes: int) -> int:
+    s = int(segment_bytes)
+    if not 1024 <= s <= 32768 or s & (s - 1):
+        raise ValueError(f"segment_bytes must be a power of two in 1024..32768, not {segment_bytes}")
+    return s
+
+
+def index_nbytes(height: int, width: int, segment_bytes: int = SEGMENT_BYTES) -> int:
+    """The bytes of the index of a height x width frame for segment_bytes (md2_png_index_bytes):
+    a 16-byte header and height * (1 + 3 width) // segment_bytes + 1 entries of 24 bytes,
+    rounded up to 16."""
+    s = check_segment_bytes(segment_bytes)
+    if not (1 <= height <= MAX_DIM and 1 <= width <= MAX_DIM):
+        raise ValueError(f"height and width must be 1..{MAX_DIM}, not {height} x {width}")
+    cap = height * (1 + 3 * width) // s + 1
+    return _align(_lib.PNG_INDEX_HEADER_BYTES + _lib.PNG_INDEX_ENTRY_BYTES * cap, 16)
+
+
+def describe_png_batch_indexed(streams: Sequence[PngStream], indexes, offsets: Sequence[int], segment_bytes: int):
+    """describe_png_batch for md2_png_run_indexed: (images, index_offsets, stream_base,
+    total_bytes).  The block starts with the image array, the uint64 index offsets follow
+    (at len(streams) * IMAGE_BYTES), then from stream_base each stream, zeros to 16 and its
+    index: the bytes of a pack record."""
+    n = len(streams)
+    if n != len(offsets) or n != len(indexes):
+        raise ValueError(f"{n} streams but {len(indexes)} indexes and {len(offsets)} offsets")
+    images = (_lib.PngImage * max(n, 1))()
+    index_offsets = (ctypes.c_uint64 * max(n, 1))()
+    pos = 0
+    for i, s in enumerate(streams):
+        want = index_nbytes(s.height, s.width, segment_bytes)
+        if len(indexes[i]) != want:
+            raise ValueError(f"stream {i}: an index of {len(indexes[i])} bytes for a {s.height} x {s.width} frame "
+                             f"(expected {want} at segment_bytes {segment_bytes})")
+        im = images[i]
+        im.height, im.width = s.height, s.width
+        im.out_offset = int(offsets[i])
+        im.stream_offset, im.stream_bytes = pos, len(s.data)
+        index_offsets[i] = pos + _align(len(s.data), 16)
+        pos += _align(len(s.data), 16) + want
+    base = _align(n * (IMAGE_BYTES + 8), 16)
+    return images, index_offsets, base, base + max(pos, 16)
+
+
+def fill_png_staging_indexed(host: np.ndarray, streams, indexes, images, index_offsets, base: int):
+    """The staging block of describe_png_batch_indexed's layout written into `host` (uint8)."""
+    n = len(streams)
+    nb = n * IMAGE_BYTES
+    host[:nb] = np.frombuffer(images, np.uint8, nb)
+    host[nb:nb + 8 * n] = np.frombuffer(index_offsets, np.uint8, 8 * n)
+    host[nb + 8 * n:base] = 0
+    for i, s in enumerate(streams):
+        o = base + images[i].stream_offset
+        host[o:o + len(s.data)] = np.frombuffer(s.data, np.uint8)
+        host[o + len(s.data):base + index_offsets[i]] = 0
+        o = base + index_offsets[i]
+        host[o:o + len(indexes[i])] = np.frombuffer(indexes[i], np.uint8)
+
+
+def check_png_described_indexed(images, index_offsets, n: int, segment_bytes: int, streams_bytes: int,
+                                out_bytes: int):
+    """md2_png_run_indexed's argument checks alone (host only): raises what it would refuse."""
+    _lib.check(_lib.lib().md2_png_check_indexed(images, index_offsets, n, int(segment_bytes), streams_bytes,
+                                                out_bytes), "md2_png_check_indexed")
+
+
 class _Plan:
     """Per device: the workspace and the status words, which grow to the largest batch seen,
     and a small ring of pinned staging blocks with the events behind their uploads."""
@@ -223,6 +298,124 @@ def run_png_staged(staged: torch.Tensor, images, n: int, base: int, total: int, 
                                  plan.workspace.numel(), out.data_ptr(), out.numel(), plan.status.data_ptr(),
                                  _lib.stream(device)), "md2_png_run")
     return plan.status[:n]
+
+
+def run_png_staged_indexed(staged: torch.Tensor, images, index_offsets, n: int, base: int, total: int,
+                           segment_bytes: int, out: torch.Tensor, device: torch.device) -> torch.Tensor:
+    """run_png_staged for a block of describe_png_batch_indexed's layout (the image array, the
+    index offsets behind it, then every stream with its index): md2_png_run_indexed's three
+    launches on the current stream.  Returns the plan's status words of the call."""
+    L = _lib.lib()
+    need = L.md2_png_indexed_workspace_bytes(images, n, int(segment_bytes))
+    if need == 0:
+        _lib.check(-1, "md2_png_indexed_workspace_bytes")
+    plan = _plan_for(device)
+    with torch.cuda.device(device):
+        plan.reserve(n, need)
+        ptr = staged.data_ptr()
+        _lib.check(L.md2_png_run_indexed(ptr + base, total - base, images, ptr, index_offsets, ptr + n * IMAGE_BYTES,
+                                         n, int(segment_bytes), plan.workspace.data_ptr(), plan.workspace.numel(),
+                                         out.data_ptr(), out.numel(), plan.status.data_ptr(), _lib.stream(device)),
+                   "md2_png_run_indexed")
+    return plan.status[:n]
+
+
+def _cuda_device(device, what: str) -> torch.device:
+    device = torch.device(device) if device is not None else torch.device("cuda")
+    if device.type != "cuda" or not torch.cuda.is_available():
+        raise RuntimeError(f"{what} is GPU only (HIP kernels, no CPU fallback)")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
+def index_png_batch(streams: Sequence[PngStream], segment_bytes: int = SEGMENT_BYTES, device=None,
+                    check: bool = True) -> List[Optional[np.ndarray]]:
+    """The index of every stream for `segment_bytes` (md2_png_index: the serial walk, one
+    wave per stream, no frame is written), as uint8 arrays of index_nbytes(h, w,
+    segment_bytes).  Waits for the status words: a stream the inflate stage refuses raises a
+    RuntimeError naming its index and bits, or with check=False gives None in its place."""
+    segment_bytes = check_segment_bytes(segment_bytes)
+    device = _cuda_device(device, "index_png_batch")
+    n = len(streams)
+    if n == 0:
+        return []
+    images, base, total = describe_png_batch(streams, [0] * n)
+    sizes = [index_nbytes(s.height, s.width, segment_bytes) for s in streams]
+    index_offsets = (ctypes.c_uint64 * n)()
+    pos = 0
+    for i, b in enumerate(sizes):
+        index_offsets[i] = pos
+        pos += b
+    off_at = _align(total, 16)             # the device copy of the offsets, behind the streams
+    plan = _plan_for(device)
+    L = _lib.lib()
+    with torch.cuda.device(device):
+        pinned, staged, r = plan.stage(off_at + 8 * n)
+        host = pinned.numpy()
+        fill_png_staging(host, streams, images, base)
+        host[off_at:off_at + 8 * n] = np.frombuffer(index_offsets, np.uint8, 8 * n)
+        staged[:off_at + 8 * n].copy_(pinned[:off_at + 8 * n], non_blocking=True)
+        if plan.events[r] is None:
+            plan.events[r] = torch.cuda.Event()
+        plan.events[r].record()
+        index = torch.empty(pos, dtype=torch.uint8, device=device)
+        status = torch.zeros(n, dtype=torch.int32, device=device)
+        ptr = staged.data_ptr()
+        _lib.check(L.md2_png_index(ptr + base, total - base, images, ptr, n, segment_bytes, index.data_ptr(), pos,
+                                   index_offsets, ptr + off_at, status.data_ptr(), _lib.stream(device)),
+                   "md2_png_index")
+        words = status.cpu().tolist()
+        flat = index.cpu().numpy()
+    bad = [i for i, w in enumerate(words) if w]
+    if bad and check:
+        raise RuntimeError(f"index_png_batch: stream index {bad[0]} did not inflate (status {words[bad[0]]}: "
+                           f"{status_text(words[bad[0]])}); bad indices {bad}")
+    return [None if words[i] else flat[index_offsets[i]:index_offsets[i] + sizes[i]].copy() for i in range(n)]
+
+
+def index_segment_bytes(index) -> int:
+    """The segment_bytes an index was made for (its bytes 4..7)."""
+    return int(np.frombuffer(bytes(index[4:8]), "<u4")[0])
+
+
+def decode_png_batch_indexed(streams: Sequence[PngStream], indexes, out: torch.Tensor, offsets: Sequence[int],
+                             device=None, check: bool = False, segment_bytes: Optional[int] = None) -> torch.Tensor:
+    """decode_png_batch from the streams' indexes (index_png_batch's, or a pack's): the same
+    contract, bytes and status words, the inflate spread over one wave per segment.  An index
+    that does not fit its stream sets _lib.PNG_ST_INDEX in the stream's word; its frame is not
+    written and the others are unaffected.  segment_bytes: what the indexes were made for
+    (default: what the first one says)."""
+    if not torch.is_tensor(out):
+        raise ValueError("out must be a uint8 tensor on the device")
+    device = _cuda_device(device if device is not None else out.device, "decode_png_batch_indexed")
+    if out.device != device or out.dtype != torch.uint8 or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous uint8 tensor on {device}")
+    n = len(streams)
+    if n == 0:
+        return torch.zeros(0, dtype=torch.int32, device=device)
+    indexes = [np.ascontiguousarray(ix, dtype=np.uint8).reshape(-1) for ix in indexes]
+    if segment_bytes is None:
+        segment_bytes = index_segment_bytes(indexes[0])
+    segment_bytes = check_segment_bytes(segment_bytes)
+    images, index_offsets, base, total = describe_png_batch_indexed(streams, indexes, offsets, segment_bytes)
+    check_png_described_indexed(images, index_offsets, n, segment_bytes, total - base, out.numel())
+    plan = _plan_for(device)
+    with torch.cuda.device(device):
+        pinned, staged, r = plan.stage(total)
+        fill_png_staging_indexed(pinned.numpy(), streams, indexes, images, index_offsets, base)
+        staged[:total].copy_(pinned[:total], non_blocking=True)
+        if plan.events[r] is None:
+            plan.events[r] = torch.cuda.Event()
+        plan.events[r].record()
+        status = run_png_staged_indexed(staged, images, index_offsets, n, base, total, segment_bytes, out, device)
+        if check:
+            bad = torch.nonzero(status.cpu()).flatten().tolist()
+            if bad:
+                word = int(status[bad[0]])
+                raise RuntimeError(f"decode_png_batch_indexed: stream index {bad[0]} did not decode (status {word}: "
+                                   f"{status_text(word)}); bad indices {bad}")
+    return status
 
 
 def decode_png_batch(streams: Sequence[PngStream], out: torch.Tensor, offsets: Sequence[int], device=None,

@@ -4,6 +4,8 @@ with and without it.  Informational; no bar is set on these numbers.
     python tools/png_bench.py [--frames 36 256] [--height 375] [--width 1242] [--repeats 5]
                               [--sections kernel pillow pack loader] [--tree-frames 640]
                               [--batch 12] [--threads 16] [--out profiles/png_decode.json]
+    python tools/png_bench.py --sections indexed [--segment-bytes 16384] --repeats 3
+                              --out profiles/png_indexed.json
 
 Workload: `texture` frames (tools/loader_bench.py) of 375 x 1242 saved by Pillow with its
 defaults (eight distinct frames, rolled sideways to make the others).
@@ -19,6 +21,11 @@ defaults (eight distinct frames, rolled sideways to make the others).
           device_png, at --batch and --threads, alternated epoch by epoch
   kernels two decode calls of the first --frames count and nothing else: the process to run under
           `rocprofv3 --kernel-trace --stats` for the per-kernel split
+  indexed (not in the default list) md2_png_run_indexed against md2_png_run on
+          the same --frames streams on the device, interval by interval in turn; the time of
+          md2_png_index; a loader epoch from a KIND_PNG pack, from a KIND_RAW pack of the same
+          tree and from the tree through PIL, epoch by epoch in turn; the bytes of both packs
+  kernels_indexed  two md2_png_run_indexed calls of the first --frames count and nothing else
 
 A run that finds no GPU fails.  Prints one JSON line and writes it to --out.
 """
@@ -111,6 +118,102 @@ def bench_kernel(files, first_frame, dev, repeats):
             "first_frame_equals_pillow": bool(np.array_equal(got, first_frame))}
 
 
+def staged_call_indexed(files, dev, segment_bytes):
+    """staged_call for md2_png_run_indexed; also returns the seconds md2_png_index took."""
+    streams = [png_ops.parse_png(f) for f in files]
+    png_ops.index_png_batch(streams[:2], segment_bytes, dev)      # warm
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    indexes = png_ops.index_png_batch(streams, segment_bytes, dev)
+    index_s = time.perf_counter() - t0
+    offsets, pos = [], 0
+    for s in streams:
+        offsets.append(pos)
+        pos += (s.height * s.width * 3 + 255) // 256 * 256
+    images, index_offsets, base, total = png_ops.describe_png_batch_indexed(streams, indexes, offsets, segment_bytes)
+    host = np.zeros(total, np.uint8)
+    png_ops.fill_png_staging_indexed(host, streams, indexes, images, index_offsets, base)
+    staged = torch.from_numpy(host).to(dev)
+    out = torch.empty(pos, dtype=torch.uint8, device=dev)
+
+    def call():
+        return png_ops.run_png_staged_indexed(staged, images, index_offsets, len(streams), base, total, segment_bytes,
+                                              out, dev)
+    return call, out, streams, offsets, index_s, sum(len(ix) for ix in indexes)
+
+
+def bench_indexed(files, first_frame, dev, repeats, segment_bytes):
+    """md2_png_run and md2_png_run_indexed on the same streams, an interval of each in turn."""
+    serial, out_s, streams, offsets = staged_call(files, dev)
+    indexed, out_i, _, _, index_s, index_bytes = staged_call_indexed(files, dev, segment_bytes)
+    times = {"serial": [], "indexed": []}
+    status = {}
+    for name, call in (("serial", serial), ("indexed", indexed)):
+        status[name] = call()
+        torch.cuda.synchronize()
+    calls = {"serial": 3, "indexed": 10}
+    for _ in range(repeats):
+        for name, call in (("serial", serial), ("indexed", indexed)):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(calls[name]):
+                status[name] = call()
+            b.record()
+            torch.cuda.synchronize()
+            times[name].append(a.elapsed_time(b) / calls[name])
+    s = streams[0]
+    got = out_i[offsets[0]:offsets[0] + s.height * s.width * 3].cpu().numpy().reshape(s.height, s.width, 3)
+    res = {"frames": len(files), "index_seconds": round(index_s, 3), "index_bytes": index_bytes,
+           "stream_bytes": sum(len(x.data) for x in streams),
+           "same_bytes_as_serial": bool(torch.equal(out_s, out_i)),
+           "first_frame_equals_pillow": bool(np.array_equal(got, first_frame))}
+    for name in times:
+        med = statistics.median(times[name])
+        res[name] = {"ms_per_call": round(med, 3), "ms_per_call_all": [round(x, 3) for x in times[name]],
+                     "frames_per_s": round(len(files) / (med * 1e-3), 1),
+                     "status_all_zero": bool(int(status[name].abs().sum()) == 0)}
+    res["speedup"] = round(res["serial"]["ms_per_call"] / res["indexed"]["ms_per_call"], 2)
+    return res
+
+
+def bench_loader_packs(root, lines, batch, threads, repeats, dev, segment_bytes):
+    """A loader epoch from a KIND_PNG pack, from a KIND_RAW pack of the same tree and from the
+    tree through PIL, epoch by epoch in turn; the packs' bytes and build times."""
+    from monodepth2_amd.datasets import KITTIRAWDataset
+    from monodepth2_amd.loader import BatchLoader
+    from monodepth2_amd.pack import FramePack, build_pack
+    out = {"batch": batch, "threads": threads, "segment_bytes": segment_bytes}
+    packs = {}
+    for name, kw in (("png_pack", dict(png_records=True, segment_bytes=segment_bytes)), ("raw_pack", {})):
+        path = os.path.join(root, name + ".pack")
+        t0 = time.perf_counter()
+        stats = build_pack(path, root, [lines], png=True, device=dev, threads=threads, **kw)
+        out[name] = {"build_seconds": round(time.perf_counter() - t0, 3), "pack_bytes": stats["pack_bytes"],
+                     "png_records": stats["png"], "raw_records": stats["raw"], "file_bytes": stats["file_bytes"]}
+        packs[name] = FramePack(path)
+    ds = KITTIRAWDataset(root, lines, H, W, FRAME_IDS, S, is_train=True, img_ext=".png")
+    loaders = {"pil": BatchLoader(ds, batch, shuffle=True, seed=0, num_workers=threads)}
+    for name, fp in packs.items():
+        loaders[name] = BatchLoader(ds, batch, shuffle=True, seed=0, num_workers=threads, pack=fp)
+    times = {name: [] for name in loaders}
+    n = 0
+    for rep in range(repeats + 1):
+        for name, ld in loaders.items():
+            ld.set_epoch(rep)
+            t, n = epoch_time(ld)
+            if rep:
+                times[name].append(t)
+    out["batches"] = n
+    for name, ld in loaders.items():
+        t = statistics.median(times[name])
+        out.setdefault(name, {}).update({"epoch_s": round(t, 3), "epoch_s_all": [round(x, 3) for x in times[name]],
+                                         "frames_per_s": round(n * batch * len(FRAME_IDS) / t, 1)})
+        ld.close()
+    for fp in packs.values():
+        fp.close()
+    return out
+
+
 def bench_pillow(files):
     def load(data):
         return np.asarray(Image.open(io.BytesIO(data)).convert("RGB")).shape[0]
@@ -195,8 +298,9 @@ def main():
     ap.add_argument("--tree-frames", type=int, default=640)
     ap.add_argument("--batch", type=int, default=12)
     ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--segment-bytes", type=int, default=png_ops.SEGMENT_BYTES, help="of the indexed sections")
     ap.add_argument("--sections", nargs="+", default=["kernel", "pillow", "pack", "loader"],
-                    choices=["kernel", "pillow", "pack", "loader", "kernels"])
+                    choices=["kernel", "pillow", "pack", "loader", "kernels", "indexed", "kernels_indexed"])
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "png_decode.json"))
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -211,6 +315,12 @@ def main():
         call()
         torch.cuda.synchronize()
         return
+    if "kernels_indexed" in args.sections:
+        call = staged_call_indexed(files[:args.frames[0]], dev, args.segment_bytes)[0]
+        call()
+        call()
+        torch.cuda.synchronize()
+        return
     result = {"height": args.height, "width": args.width, "repeats": args.repeats, "synthetic_inputs": True,
               "mean_file_bytes": round(sum(map(len, files)) / len(files)), "device": torch.cuda.get_device_name(0)}
     for section in ("kernel", "pillow", "pack", "loader"):
@@ -219,6 +329,21 @@ def main():
         result["kernel"] = [bench_kernel(files[:n], frames[0], dev, args.repeats) for n in args.frames]
     if "pillow" in args.sections:
         result["pillow"] = bench_pillow(files[:min(max(args.frames), 64)])
+    if "indexed" in args.sections:
+        # LDS per workgroup of the segment kernel: (S + 264) 16-bit symbols, the 2 KiB input buffer and
+        # the tables (8416 bytes with the input buffer: what png_index_kernel, which has no window, takes)
+        result["indexed"] = {"segment_bytes": args.segment_bytes,
+                             "segment_kernel_lds_bytes": 2 * (args.segment_bytes + 264) + 8416,
+                             "kernel": [bench_indexed(files[:n], frames[0], dev, min(args.repeats, 3),
+                                                      args.segment_bytes) for n in args.frames]}
+        root = tempfile.mkdtemp(prefix="md2_pngbench_")
+        try:
+            lines, size = write_tree(root, args.tree_frames, args.height, args.width)
+            result["tree"] = {"frames": args.tree_frames, "png_bytes": size}
+            result["indexed"]["loader"] = bench_loader_packs(root, lines, args.batch, args.threads,
+                                                             min(args.repeats, 3), dev, args.segment_bytes)
+        finally:
+            shutil.rmtree(root, ignore_errors=True)
     if "pack" in args.sections or "loader" in args.sections:
         root = tempfile.mkdtemp(prefix="md2_pngbench_")
         try:
