@@ -1293,6 +1293,68 @@ int md2_png_run_indexed(const uint8_t* streams, uint64_t streams_bytes, const md
                         size_t workspace_bytes, uint8_t* out, uint64_t out_bytes, uint32_t* status, void* stream);
 
 /*
+ * PNG encoding on the device (csrc/pngenc.hip): the other half of md2_png_run.  Tight
+ * (height, width, 3) uint8 RGB frames (MD2_PNGENC_RGB8: colour type 2, depth 8) and (height,
+ * width) 16-bit grey maps in host byte order (MD2_PNGENC_GRAY16: colour type 0, depth 16,
+ * written big-endian; int16 storage holds the uint16 bit patterns, as md2_depth_export16
+ * leaves them), of mixed sizes and kinds -> the complete zlib stream of each file's IDAT chunk
+ * (2-byte header, deflate blocks, Adler-32).  The host writes the signature, IHDR, IDAT, IEND
+ * and their CRCs around it (monodepth2_amd/png_ops.py).  The bytes follow the format rules of
+ * DESIGN.md §6n (per-row filter choice, segments of segment_bytes filtered bytes that are
+ * compressed independently, one deflate block each and an empty stored block behind every
+ * segment but the last, the candidate and parse rule, the code construction); they are not
+ * zlib's bytes, and every stream is one zlib's inflate accepts.  Integer arithmetic only;
+ * the atomics are integer (LDS max/add, OR on a wave's own zeroed words): two runs are
+ * bit-equal.  New symbols under ABI 24, no version bump (as md2_jpeg_encode).
+ *
+ * in: device bytes, 2-byte aligned; frame i is height * width * 3 (RGB8) or * 2 (GRAY16)
+ * bytes at in_offset (GRAY16: a multiple of 2).  images: HOST array of n, read for the checks
+ * and the launch sizes only; dev_images: a DEVICE copy of the same array (8-byte aligned),
+ * which the kernels read.  workspace: device bytes, 256-byte aligned,
+ * md2_png_encode_workspace_bytes of the batch, no initialisation needed; image i's range
+ * starts at ws_offset, which must be the sum of md2_png_encode_workspace_bytes(&images[k], 1)
+ * over k < i.  out: device bytes; image i owns out_capacity bytes at out_offset (any
+ * alignment).  stream_bytes, status: device uint32[n], written by the call: the stream's
+ * length (also when it does not fit, so the caller can size a second call) and 0 or
+ * MD2_PNGENC_ST_SPACE.  A stream that does not fit its capacity writes nothing of its range;
+ * no byte outside an image's range is written in either case and the other images of the
+ * batch are unaffected.
+ *
+ * Three launches on `stream` (filter + row sums: one wave per row; deflate: one wave per
+ * segment; pack: one block per image), no allocation, no host synchronisation,
+ * hipGraph-capturable.  Refused (MD2_ERR_ARG) before anything is launched: NULL arguments, n
+ * outside 1..4096, a height or width outside 1..8192, an unknown kind, a segment_bytes that is
+ * no power of two in 1024..32768, a frame that leaves in_bytes, an odd in_offset of a 16-bit
+ * frame, an output range that leaves out_bytes, a ws_offset that is not the running sum, a
+ * non-zero reserved word, misaligned buffers, a workspace that is too small.
+ * md2_png_encode_check runs the checks that need no pointer alone (host only, launches
+ * nothing).  md2_png_encode_bound: a capacity no stream of that geometry exceeds (every
+ * segment stored, n + 5, and flushed, 5; header 2 and trailer 4: total + 10 * segments + 6),
+ * 0 (and md2_last_error) for a geometry the encoder refuses.
+ */
+#define MD2_PNGENC_RGB8   0
+#define MD2_PNGENC_GRAY16 1
+#define MD2_PNGENC_ST_SPACE (1u << 0)   /* the stream does not fit out_capacity */
+
+typedef struct md2_pngenc_image {
+    uint64_t in_offset;             /* bytes into in: the tight frame */
+    uint64_t out_offset;            /* bytes into out */
+    uint64_t ws_offset;             /* bytes into workspace: the running sum of the images before */
+    uint32_t out_capacity;          /* bytes of the output range */
+    int32_t height, width;          /* 1..8192 */
+    int32_t kind;                   /* MD2_PNGENC_RGB8 / MD2_PNGENC_GRAY16 */
+    int32_t segment_bytes;          /* S: a power of two in 1024..32768 */
+    uint32_t reserved;              /* 0; the struct is 48 bytes */
+} md2_pngenc_image;
+
+size_t md2_png_encode_bound(int height, int width, int kind, int segment_bytes);
+size_t md2_png_encode_workspace_bytes(const md2_pngenc_image* images, int n);
+int md2_png_encode_check(const md2_pngenc_image* images, int n, uint64_t in_bytes, uint64_t out_bytes);
+int md2_png_encode(const uint8_t* in, uint64_t in_bytes, const md2_pngenc_image* images,
+                   const md2_pngenc_image* dev_images, int n, void* workspace, size_t workspace_bytes, uint8_t* out,
+                   uint64_t out_bytes, uint32_t* stream_bytes, uint32_t* status, void* stream);
+
+/*
  * The training log's pictures (csrc/md2hot.hip): what the reference's Trainer.log writes at
  * a log step (trainer.py:540-572, with normalize_image, utils.py:22-28) for the first
  * `items` images of the batch, as one uint8 contact sheet (items, sheet_h, sheet_w, 3) filled

@@ -85,6 +85,7 @@ EXPORTS = ["md2_abi_version", "md2_last_error", "md2_workspace_bytes", "md2_sele
            "md2_png_workspace_bytes", "md2_png_check", "md2_png_run",
            "md2_png_index_bytes", "md2_png_indexed_workspace_bytes", "md2_png_index", "md2_png_check_indexed",
            "md2_png_run_indexed",
+           "md2_png_encode_bound", "md2_png_encode_workspace_bytes", "md2_png_encode_check", "md2_png_encode",
            "md2_log_panel_tile_blocks", "md2_log_panel_check", "md2_log_panel_workspace_bytes", "md2_log_panel",
            "md2_depth_points", "md2_depth_points_workspace_bytes"]
 
@@ -278,6 +279,17 @@ class PngImage(ctypes.Structure):
                 ("stream_offset", ctypes.c_uint64), ("stream_bytes", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+# md2_png_encode (csrc/pngenc.hip): new symbols under ABI 24, no version bump
+PNGENC_RGB8, PNGENC_GRAY16 = 0, 1
+PNGENC_ST_SPACE = 1      # the stream does not fit its output range
+
+
+class PngEncImage(ctypes.Structure):
+    _fields_ = [("in_offset", ctypes.c_uint64), ("out_offset", ctypes.c_uint64), ("ws_offset", ctypes.c_uint64),
+                ("out_capacity", ctypes.c_uint32), ("height", ctypes.c_int32), ("width", ctypes.c_int32),
+                ("kind", ctypes.c_int32), ("segment_bytes", ctypes.c_int32), ("reserved", ctypes.c_uint32)]
+
+
 # md2_log_panel (csrc/md2hot.hip): new symbols under ABI 24, no version bump
 LOG_COLOR, LOG_WARP, LOG_DISP, LOG_MAP = 0, 1, 2, 3
 LOG_MAX_ITEMS = 4
@@ -376,6 +388,15 @@ def _declare(L):
     L.md2_png_run_indexed.restype = ctypes.c_int
     L.md2_png_run_indexed.argtypes = [_vp, ctypes.c_uint64, ctypes.POINTER(PngImage), _vp, _u64p, _vp, ctypes.c_int,
                                       ctypes.c_int, _vp, ctypes.c_size_t, _vp, ctypes.c_uint64, _vp, _vp]
+    L.md2_png_encode_bound.restype = ctypes.c_size_t
+    L.md2_png_encode_bound.argtypes = [ctypes.c_int] * 4
+    L.md2_png_encode_workspace_bytes.restype = ctypes.c_size_t
+    L.md2_png_encode_workspace_bytes.argtypes = [ctypes.POINTER(PngEncImage), ctypes.c_int]
+    L.md2_png_encode_check.restype = ctypes.c_int
+    L.md2_png_encode_check.argtypes = [ctypes.POINTER(PngEncImage), ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64]
+    L.md2_png_encode.restype = ctypes.c_int
+    L.md2_png_encode.argtypes = [_vp, ctypes.c_uint64, ctypes.POINTER(PngEncImage), _vp, ctypes.c_int, _vp,
+                                 ctypes.c_size_t, _vp, ctypes.c_uint64, _vp, _vp, _vp]
     L.md2_depth_export16.restype = ctypes.c_int
     L.md2_depth_export16.argtypes = [ctypes.POINTER(Depth16Desc)] + [_vp] * 4
     L.md2_depth_export16_check.restype = ctypes.c_int

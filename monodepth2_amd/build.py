@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB_NAME = "libmd2hot.so"
 LIB_PATH = os.path.join(CSRC, LIB_NAME)
-SOURCES = ["md2hot.hip", "decoder.hip", "pose.hip", "augment.hip", "bnorm.hip", "pool.hip", "adam.hip", "disphead.hip", "stem.hip", "bias_act.hip", "conv.hip", "direct.hip", "glue.hip", "eval.hip", "velo.hip", "traj.hip", "viz.hip", "jpeg.hip", "points.hip", "jpegenc.hip", "png.hip"]
+SOURCES = ["md2hot.hip", "decoder.hip", "pose.hip", "augment.hip", "bnorm.hip", "pool.hip", "adam.hip", "disphead.hip", "stem.hip", "bias_act.hip", "conv.hip", "direct.hip", "glue.hip", "eval.hip", "velo.hip", "traj.hip", "viz.hip", "jpeg.hip", "points.hip", "jpegenc.hip", "png.hip", "pngenc.hip"]
 HEADERS = [os.path.join(INCLUDE, "md2hot.h"), os.path.join(CSRC, "md2_bf16.h"), os.path.join(CSRC, "md2_bn_expr.h"),
            os.path.join(CSRC, "md2_x6.h")]
 ARCH = os.environ.get("MD2_OFFLOAD_ARCH", "gfx950")
@@ -85,6 +85,7 @@ BUILD_ID_MARKER = b"md2-build-id:"
 # coefficients can pass 32 bits, and what it gives then must be defined (and unused).
 # png.hip needs no flag: unsigned integer arithmetic throughout (it wraps by definition), the
 # few signed values (Paeth's sums, canonical codes) stay below 2^17, and no floating point.
+# pngenc.hip likewise: unsigned arithmetic, Paeth's sums the only signed values.
 FLAGS = {"md2hot.hip": ["-fno-slp-vectorize", "-mllvm", "--amdgpu-sched-strategy=iterative-ilp"],
          "conv.hip": ["-mllvm", "--amdgpu-sched-strategy=max-ilp"],
          "bnorm.hip": ["-mllvm", "--amdgpu-sched-strategy=max-ilp"],

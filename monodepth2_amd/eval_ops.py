@@ -201,12 +201,30 @@ def benchmark_depth_maps(disp: torch.Tensor, post_process_disp: Optional[torch.T
     return out
 
 
-def write_benchmark_pngs(maps, save_dir: str, start: int = 0):
+def write_benchmark_pngs(maps, save_dir: str, start: int = 0, device_encode: bool = False):
     """`maps` (N, OH, OW), benchmark_depth_maps' int16 tensor or a uint16 / int16 array, as
     the files `{:010d}.png` of `save_dir`, numbered from `start`: 16-bit greyscale PNGs
-    (Pillow mode I;16), what evaluate_depth.py:161-162 writes through cv2.  Returns the paths."""
+    (Pillow mode I;16), what evaluate_depth.py:161-162 writes through cv2.  Returns the paths.
+    device_encode: the int16 device tensor is filtered and deflated where it lies
+    (png_ops.encode_png_batch) and only the compressed bytes come to the host:
+    the same pixels in files of other bytes.  GPU only."""
     import os
 
+    if device_encode:
+        from . import png_ops
+        if not torch.is_tensor(maps) or not maps.is_cuda:
+            raise RuntimeError("write_benchmark_pngs(device_encode=True) is GPU only (HIP kernels, no CPU fallback)")
+        if maps.dim() != 3 or maps.dtype != torch.int16:
+            raise ValueError(f"maps must be (N, OH, OW) int16, got {tuple(maps.shape)} {maps.dtype}")
+        files = png_ops.encode_png_batch(maps.contiguous(), kind=png_ops.KIND_GRAY16)
+        os.makedirs(save_dir, exist_ok=True)
+        paths = []
+        for i, data in enumerate(files):
+            path = os.path.join(save_dir, "{:010d}.png".format(start + i))
+            with open(path, "wb") as f:
+                f.write(data)
+            paths.append(path)
+        return paths
     from PIL import Image
     arr = maps.cpu().numpy() if torch.is_tensor(maps) else np.asarray(maps)
     if arr.ndim != 3 or arr.dtype not in (np.int16, np.uint16):

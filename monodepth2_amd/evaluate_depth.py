@@ -275,7 +275,8 @@ def export_benchmark(pred, flipped, scaled: bool, opt, save_dir: str, device, ch
                                     to_dev(flipped[i:i + chunk]) if flipped is not None else None,
                                     out_hw=BENCHMARK_HW, scale_factor=STEREO_SCALE_FACTOR, clip_max=80.0, quant=256.0,
                                     min_depth=min_depth, max_depth=max_depth)
-        paths += write_benchmark_pngs(maps, save_dir, start=i)
+        paths += write_benchmark_pngs(maps, save_dir, start=i,
+                                      device_encode=bool(getattr(opt, "device_png_encode", False)))
     return paths
 
 

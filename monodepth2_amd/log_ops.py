@@ -224,18 +224,28 @@ def log_panel(cfg: HotPathConfig, inputs: Dict, outputs: Dict, frame_ids: Sequen
     return run_tiles(cfg, n, (SH, SW), tags, specs, disps, warp, plan)
 
 
-def write_panel(panel: LogPanel, folder: str, step: int) -> List[str]:
+def write_panel(panel: LogPanel, folder: str, step: int, device_encode: bool = False) -> List[str]:
     """step_{step:07d}_{j}.png per logged image under `folder`, and once per folder
     layout.json (tag -> [y, x, h, w]).  The one copy of the sheet to the host is the only
-    synchronisation of a log step's pictures."""
-    from PIL import Image
+    synchronisation of a log step's pictures.  device_encode: the sheet is filtered and
+    deflated on the device (png_ops.encode_png_batch) and the compressed bytes
+    are what is copied: the same pixels in files of other bytes."""
     os.makedirs(folder, exist_ok=True)
-    host = panel.sheet.cpu().numpy()
     paths = []
-    for j in range(host.shape[0]):
-        p = os.path.join(folder, "step_{:07d}_{}.png".format(int(step), j))
-        Image.fromarray(host[j]).save(p)
-        paths.append(p)
+    if device_encode:
+        from . import png_ops
+        for j, data in enumerate(png_ops.encode_png_batch(panel.sheet, kind=png_ops.KIND_RGB8)):
+            p = os.path.join(folder, "step_{:07d}_{}.png".format(int(step), j))
+            with open(p, "wb") as f:
+                f.write(data)
+            paths.append(p)
+    else:
+        from PIL import Image
+        host = panel.sheet.cpu().numpy()
+        for j in range(host.shape[0]):
+            p = os.path.join(folder, "step_{:07d}_{}.png".format(int(step), j))
+            Image.fromarray(host[j]).save(p)
+            paths.append(p)
     lj = os.path.join(folder, "layout.json")
     if not os.path.exists(lj):
         with open(lj, "w") as f:

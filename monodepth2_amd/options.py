@@ -28,6 +28,11 @@ _FLAGS = [
     ("--device_png", dict(action="store_true", help="build: decode 8-bit RGB PNG frames on the GPU too (inflate "
                                                      "and unfilter in HIP kernels, bit-equal to PIL); implies "
                                                      "--device_decode; other files still go through PIL")),
+    ("--device_png_encode", dict(action="store_true", help="build: write the PNG outputs (the benchmark split's "
+                                                            "16-bit depth maps, the --log_images contact sheets) "
+                                                            "filtered and deflated on the GPU (HIP kernels, "
+                                                            "lossless; the files differ from Pillow's in their "
+                                                            "bytes, not in their pixels)")),
     ("--pack", dict(type=str, help="build: feed the frames from this packed frame file (python -m "
                                    "monodepth2_amd.pack_dataset) instead of the image files under --data_path; "
                                    "implies --device_decode; ground-truth depth is still read from --data_path")),

@@ -21,6 +21,11 @@ finds the indexes on the device (once: a frame pack keeps them behind the stream
 `index_nbytes(h, w, segment_bytes)` is an index's size (fixed per geometry), and
 `decode_png_batch_indexed(streams, indexes, out, offsets)` is `decode_png_batch` from them:
 the same bytes and status words, or `_lib.PNG_ST_INDEX` for an index that does not fit.
+
+The encoder (`md2_png_encode`, csrc/pngenc.hip) is the way back:
+`encode_png_batch(frames)` turns device frames (8-bit RGB, 16-bit grey) into the bytes of PNG
+files, filtered and deflated on the device by the rules of §6n; `png_file_bytes` wraps a zlib
+stream in the chunks.  Lossless, deterministic, and not zlib's bytes.
 """
 from __future__ import annotations
 
@@ -483,3 +488,164 @@ def decode_png_frames(streams: Sequence[PngStream], device=None, names: Optional
         raise RuntimeError(f"{who} did not decode on the device (status {status[bad[0]]}: "
                            f"{status_text(status[bad[0]])}); {len(bad)} bad file(s) in its batch")
     return flat, offsets, sizes
+
+
+# ------------------------------------------------------------------ encoding (csrc/pngenc.hip)
+KIND_RGB8, KIND_GRAY16 = _lib.PNGENC_RGB8, _lib.PNGENC_GRAY16
+ENC_IMAGE_BYTES = ctypes.sizeof(_lib.PngEncImage)
+_BPP = {KIND_RGB8: 3, KIND_GRAY16: 2}
+
+
+def _chunk(kind: bytes, body: bytes) -> bytes:
+    return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body))
+
+
+def png_file_bytes(height: int, width: int, kind: int, zlib_stream) -> bytes:
+    """The PNG file around one zlib stream: signature, IHDR (depth 8 colour type 2 for
+    KIND_RGB8, depth 16 colour type 0 for KIND_GRAY16, not interlaced), one IDAT, IEND."""
+    if kind not in _BPP:
+        raise ValueError(f"unknown kind {kind}")
+    depth, colour = (8, 2) if kind == KIND_RGB8 else (16, 0)
+    ihdr = struct.pack(">IIBBBBB", int(width), int(height), depth, colour, 0, 0, 0)
+    return SIGNATURE + _chunk(b"IHDR", ihdr) + _chunk(b"IDAT", bytes(zlib_stream)) + _chunk(b"IEND", b"")
+
+
+def encode_bound(height: int, width: int, kind: int, segment_bytes: int = SEGMENT_BYTES) -> int:
+    """md2_png_encode_bound: a capacity no zlib stream of that geometry exceeds."""
+    b = _lib.lib().md2_png_encode_bound(int(height), int(width), int(kind), int(segment_bytes))
+    if b == 0:
+        _lib.check(-1, "md2_png_encode_bound")
+    return b
+
+
+def describe_png_encode(geometries, in_offsets: Sequence[int], capacities: Optional[Sequence[int]] = None):
+    """The host side of a call.  geometries: (height, width, kind, segment_bytes) per image;
+    in_offsets: where each frame starts in the input bytes; capacities: the output range of
+    each (default: encode_bound).  Returns (images, out_bytes, workspace_bytes): the
+    md2_pngenc_image array with the output ranges laid out one after the other at 16-byte
+    aligned offsets and the workspace ranges as the running sum."""
+    L = _lib.lib()
+    n = len(geometries)
+    if n != len(in_offsets) or (capacities is not None and n != len(capacities)):
+        raise ValueError(f"{n} geometries but {len(in_offsets)} offsets")
+    images = (_lib.PngEncImage * max(n, 1))()
+    out_pos = ws_pos = 0
+    for i, (h, w, kind, s) in enumerate(geometries):
+        im = images[i]
+        im.height, im.width, im.kind, im.segment_bytes = int(h), int(w), int(kind), int(s)
+        need = L.md2_png_encode_workspace_bytes(ctypes.byref(im), 1)
+        if need == 0:
+            _lib.check(-1, "md2_png_encode_workspace_bytes")
+        cap = encode_bound(h, w, kind, s) if capacities is None else int(capacities[i])
+        im.in_offset, im.out_offset, im.ws_offset, im.out_capacity = int(in_offsets[i]), out_pos, ws_pos, cap
+        out_pos += _align(max(cap, 1), 16)
+        ws_pos += need
+    return images, max(out_pos, 16), ws_pos
+
+
+def check_png_encode_described(images, n: int, in_bytes: int, out_bytes: int):
+    """md2_png_encode's argument checks alone (host only): raises what it would refuse."""
+    _lib.check(_lib.lib().md2_png_encode_check(images, n, in_bytes, out_bytes), "md2_png_encode_check")
+
+
+_enc_workspaces: Dict[torch.device, torch.Tensor] = {}
+
+
+def run_png_encode(flat: torch.Tensor, images, n: int, out: torch.Tensor, workspace_bytes: int,
+                   device: torch.device):
+    """The launches of a call on the current stream: `flat` the input bytes (uint8 view of the
+    frames on the device), `images` describe_png_encode's array, `out` the uint8 output bytes.
+    Returns (stream_bytes, status): uint32 words per image as int32 tensors on the device."""
+    L = _lib.lib()
+    with torch.cuda.device(device):
+        ws = _enc_workspaces.get(device)
+        if ws is None or ws.numel() < workspace_bytes:
+            ws = _enc_workspaces[device] = torch.empty(workspace_bytes + workspace_bytes // 8, dtype=torch.uint8,
+                                                       device=device)
+        table = torch.frombuffer(bytearray(bytes(images)[:n * ENC_IMAGE_BYTES]), dtype=torch.uint8).to(device)
+        words = torch.zeros(2 * n, dtype=torch.int32, device=device)
+        _lib.check(L.md2_png_encode(flat.data_ptr(), flat.numel(), images, table.data_ptr(), n, ws.data_ptr(),
+                                    ws.numel(), out.data_ptr(), out.numel(), words.data_ptr(),
+                                    words.data_ptr() + 4 * n, _lib.stream(device)), "md2_png_encode")
+    return words[:n], words[n:]
+
+
+def _frame_kind(t: torch.Tensor, kind) -> int:
+    if kind is None:
+        if t.dtype == torch.uint8 and t.dim() == 3 and t.shape[2] == 3:
+            return KIND_RGB8
+        if t.dtype in (torch.int16, getattr(torch, "uint16", torch.int16)) and t.dim() == 2:
+            return KIND_GRAY16
+        raise ValueError(f"cannot tell the kind of a {t.dtype} frame of shape {tuple(t.shape)}: (h, w, 3) uint8 "
+                         f"is RGB8, (h, w) int16 / uint16 is GRAY16")
+    kind = int(kind)
+    ok = (t.dtype == torch.uint8 and t.dim() == 3 and t.shape[2] == 3) if kind == KIND_RGB8 else \
+        (kind == KIND_GRAY16 and t.dtype in (torch.int16, getattr(torch, "uint16", torch.int16)) and t.dim() == 2)
+    if not ok:
+        raise ValueError(f"a {t.dtype} frame of shape {tuple(t.shape)} is not of kind {kind}")
+    return kind
+
+
+def _bytes_view(t: torch.Tensor) -> torch.Tensor:
+    return t.contiguous().view(torch.uint8).reshape(-1)
+
+
+def encode_png_batch(frames, kind=None, segment_bytes=SEGMENT_BYTES, device=None, check: bool = False) -> List[bytes]:
+    """The PNG files of device frames, filtered and deflated on the device (md2_png_encode,
+    DESIGN.md §6n).  frames: a list of tensors — (h, w, 3) uint8 is 8-bit RGB, (h, w) int16 or
+    uint16 (the uint16 bit patterns, as eval_ops.benchmark_depth_maps returns them) is 16-bit
+    grey; sizes and kinds may be mixed — or one stacked tensor (N, h, w, 3) / (N, h, w), which
+    is encoded where it lies.  kind: None (told from dtype and shape), a KIND_* or one per
+    frame; segment_bytes: S, or one per frame.  One small download of the stream lengths and
+    status words, then one of the compressed bytes, gathered on the device.  check=True also
+    inflates every stream on the host and compares its length with the scanlines'.  GPU only."""
+    stacked = torch.is_tensor(frames)
+    items = list(frames.unbind(0)) if stacked else list(frames)
+    if device is None and items and torch.is_tensor(items[0]) and items[0].is_cuda:
+        device = items[0].device
+    device = _cuda_device(device, "encode_png_batch")
+    n = len(items)
+    if n == 0:
+        return []
+    if any(not torch.is_tensor(t) or t.device != device for t in items):
+        raise RuntimeError(f"encode_png_batch is GPU only (HIP kernels, no CPU fallback): every frame must be a "
+                           f"tensor on {device}")
+    kinds = [_frame_kind(t, k) for t, k in zip(items, kind if isinstance(kind, (list, tuple)) else [kind] * n)]
+    segs = [check_segment_bytes(s) for s in
+            (segment_bytes if isinstance(segment_bytes, (list, tuple)) else [segment_bytes] * n)]
+    if len(segs) != n:
+        raise ValueError(f"{n} frames but {len(segs)} segment sizes")
+    geos = [(int(t.shape[0]), int(t.shape[1]), k, s) for t, k, s in zip(items, kinds, segs)]
+    sizes = [h * w * _BPP[k] for h, w, k, _ in geos]
+    with torch.cuda.device(device):
+        if stacked and frames.is_contiguous():
+            flat = frames.view(torch.uint8).reshape(-1)
+            offsets = [i * sizes[0] for i in range(n)]
+        else:
+            offsets, pos = [], 0
+            for b in sizes:
+                offsets.append(pos)
+                pos += _align(b, 16)
+            flat = torch.zeros(max(pos, 16), dtype=torch.uint8, device=device)
+            for t, o, b in zip(items, offsets, sizes):
+                flat[o:o + b] = _bytes_view(t)
+        images, out_bytes, ws_bytes = describe_png_encode(geos, offsets)
+        check_png_encode_described(images, n, flat.numel(), out_bytes)
+        out = torch.empty(out_bytes, dtype=torch.uint8, device=device)
+        lengths, status = run_png_encode(flat, images, n, out, ws_bytes, device)
+        words = torch.cat([lengths, status]).cpu().tolist()
+        lengths, status = words[:n], words[n:]
+        bad = [i for i, w in enumerate(status) if w]
+        if bad:
+            raise RuntimeError(f"encode_png_batch: frame index {bad[0]} needs {lengths[bad[0]]} bytes, more than "
+                               f"its bound {images[bad[0]].out_capacity}; bad indices {bad}")
+        host = torch.cat([out[images[i].out_offset:images[i].out_offset + lengths[i]] for i in range(n)]).cpu()
+        host = host.numpy().tobytes()
+    files, pos = [], 0
+    for (h, w, k, _), nb in zip(geos, lengths):
+        z = host[pos:pos + nb]
+        pos += nb
+        if check and len(zlib.decompress(z)) != h * (1 + _BPP[k] * w):
+            raise RuntimeError("encode_png_batch: a stream does not inflate to its scanlines")
+        files.append(png_file_bytes(h, w, k, z))
+    return files

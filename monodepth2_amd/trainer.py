@@ -796,7 +796,8 @@ class Trainer:
                                       plan=self._log_plans.get(mode))
         self._log_plans[mode] = panel.plan
         log_ops.write_panel(panel, os.path.join(self.log_path, mode, "images"),
-                            self.step if step is None else step)
+                            self.step if step is None else step,
+                            device_encode=bool(getattr(self.opt, "device_png_encode", False)))
         return panel
 
     def val_step(self, inputs):
